@@ -725,6 +725,8 @@ def run_tree(args, torch, dist, rank, world, local_rank, coll_device, backend_na
     if rank == 0:
         import hashlib
         roots = [r.to_postcard() if isinstance(r, p3r.BatchStarkProof) else r for r in roots]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {f"root_proof_{t}": np.frombuffer(r, dtype=np.uint8) for t, r in enumerate(roots)})
         for root in roots:
             rp = p3r.BatchStarkProof.from_postcard(root, field, zk=args.zk)    # the root is checked from its wire form
             try:
@@ -861,7 +863,7 @@ def rank_report(torch, dist, world, backend, local_rank, coll_device, rank_ms=No
 CONTRACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                  "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "proof_verified", "proof_sha256")
 CONTRACT_MAX_CHARS = 6000
-SUSTAINED_S = 6.0   # seconds of back-to-back headline proofs after the timed region (default run, one GPU)   # the driver keeps an ~8 KB tail of stdout: the final line must fit whole inside it
+SUSTAINED_S = 6.0   # seconds of back-to-back headline proofs after the timed region (--full, one GPU)   # the driver keeps an ~8 KB tail of stdout: the final line must fit whole inside it
 
 
 def _round_floats(x, digits=6):
@@ -950,6 +952,65 @@ def write_detail(full, path):
             print(f"bench: could not write {p}: {e}", file=sys.stderr)
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: what the timed path returned to its caller in its last step, one DIR/<name>.npy per array, in
+    float32 (a proof's bytes are exact in it).  The inputs are fixed by the arguments, so two builds can be compared file
+    by file.  An array beyond its share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of its elements."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def table_widths(ctx, packing):
+    """Main-trace widths of the five tables of the headline layer (const, public, alu, poseidon2, recompose)."""
+    k = packing.horner_packed_steps
+    return [4, 4 * packing.public_lanes, 16 * packing.alu_lanes + ((k - 1) // 2 + 2 * (k - 1) + 1) * 4,
+            ctx.poseidon2_trace_width, 4 * packing.recompose_lanes]
+
+
+def headline_line(args, world, ms_per_step, pc, cpd, widths, counts, proof, perms):
+    """The fields that state the headline itself: all a plain run prints; --full adds its measurements to them."""
+    import hashlib
+    field, log_h = args.field, args.log_height
+    return {
+        "metric": "prove_next_layer ms + Poseidon2 perms/s, KoalaBear 2^20-row circuit, 1/8 GPU",
+        "value": ms_per_step,
+        "unit": "ms",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": False,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32 Montgomery (31-bit prime field, degree-4 extension); Poseidon2 hashing as exact integers in f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"prove_next_layer (verifier-circuit run on the device + prove_all_tables) of the synthetic "
+                        f"{field} 2^{log_h}-row recursion layer: tables const/public/alu/poseidon2/recompose, "
+                        f"FRI blowup 4, arity<=4, 54 queries, 15-bit PoW; circuit inputs + NextLayerPrepCache "
+                        f"resident in HBM",
+            "circuit_levels": pc.levels,
+            "field": field, "log_height": log_h, "table_heights": cpd.table_heights, "table_widths": widths,
+            "ops": dict(zip(["const", "public", "alu", "poseidon2", "recompose", "witnesses", "circuit_ops"], counts)),
+            "fri": FRI, "independent_proofs": world, "proof_bytes": len(proof),
+            "parallelism": f"{world} independent proofs, one per GPU, no data-path collective",
+        },
+        "proof_verified": None,   # --full verifies the timed proof
+        "proof_sha256": hashlib.sha256(proof).hexdigest(),
+        "poseidon2_perms_per_s": perms * world / (ms_per_step * 1e-3),
+        "poseidon2_perms_per_step": perms,
+    }
+
+
 _FINAL_LINE = []
 
 
@@ -1005,9 +1066,14 @@ def main():
     ap.add_argument("--spans", action="store_true",
                     help="print the per-stage timers as tracing-forest spans under the reference's span names (stderr)")
     ap.add_argument("--full", action="store_true",
-                    help="also run the secondary legs (config 2 knobs, config 0 base layer, D = 5, width-32 table, arity-4 MMCS, "
-                         "ZK) and the second, 4x larger CPU sample: the profile rounds' form; the default run is the headline "
-                         "with its roofline and cpu_baseline and finishes in well under a minute")
+                    help="everything beyond the headline: verification of the timed proof, roofline and per-kernel figures "
+                         "(profiled steps), cpu_baseline (two CPU samples), H2D-inclusive / prep-miss / small-layer / sustained "
+                         "numbers, the multi-rank hand-off and the secondary legs (config 2 knobs, config 0 base layer, D = 5, "
+                         "width-32 table, arity-4 MMCS, ZK); the profile rounds' form.  Without it a run sets up, warms up, "
+                         "times --steps proofs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32): the headline's proof bytes, a tree run's root proofs")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where everything that is not a contract field goes (the final stdout line stays under "
                          f"{CONTRACT_MAX_CHARS} characters)")
@@ -1026,6 +1092,10 @@ def main():
                     help="--tree: independent trees in flight (0 = one per rank: the throughput form, weak scaling); tree t "
                          "is placed with rank offset t, so every rank proves the same number of nodes")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.spans and not (args.full or args.tree):
+        ap.error("--spans prints the profiled steps of a --full run")
     if not args.full:
         args.no_quintic = args.no_config2 = True
 
@@ -1106,7 +1176,7 @@ def main():
     # production-size layers first, on a quiet GPU: eight concurrent provers (their own contexts); measured after the
     # 2^20-row work of this process the same call reads 15 % lower
     small_tput = None
-    if rank == 0 and world == 1 and not args.no_small_layers:
+    if args.full and rank == 0 and world == 1 and not args.no_small_layers:
         small_tput = small_layer_throughput(p3r, wl, packing, field)
     ctx = p3r.Context(field=field, device=local_rank, **FRI)
     arrs = harness_lib.generate(field, log_h, seed=0x5EED0000 + rank, **GEN_KNOBS)
@@ -1122,17 +1192,34 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    proof_len = 0
     last_proof = b""
     for _ in range(args.warmup):
-        proof_len = len(pc.prove(resident))
+        pc.prove(resident)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         last_proof = pc.prove(resident)
-        proof_len = len(last_proof)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"proof": np.frombuffer(last_proof, dtype=np.uint8)})
+    if not args.full:
+        # a plain run: the headline and nothing else (every other measurement and check is behind --full)
+        if dist is not None:   # the step of N ranks is the slowest rank's
+            t = torch.tensor([dt], dtype=torch.float64, device=coll_device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        if rank == 0:
+            widths = table_widths(ctx, packing)
+            perms = workload_model(field, cpd.table_heights, widths, packing)[0]
+            emit(headline_line(args, world, dt / args.steps * 1e3, pc, cpd, widths, counts, last_proof, perms), args)
+        resident.free()
+        pc.free()
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        flush_final_line()
+        return
     # final hand-off of the finished proofs to rank 0 over RCCL/xGMI (outside the timed region:
     # it is one ~0.6 MB message per rank and has no counterpart in the reference)
     handoff_ms = None
@@ -1150,8 +1237,6 @@ def main():
     # What was timed is checked: the last proof of the timed region goes through verify_all_tables
     # (batch_stark_prover.rs:1230-1268; native host verifier of the C-ABI library), as every layer
     # does in recursion/examples/recursive_fibonacci.rs:444-454.  A rejected proof fails the run.
-    import hashlib
-    proof_sha256 = hashlib.sha256(last_proof).hexdigest()
     v0 = time.perf_counter()
     try:
         cache.prover.verify_all_tables(cache.prover.wrap_proof(last_proof, cpd))
@@ -1253,10 +1338,7 @@ def main():
     del arrs
 
     if rank == 0:
-        p2w = ctx.poseidon2_trace_width
-        k = packing.horner_packed_steps
-        widths = [4, 4 * packing.public_lanes, 16 * packing.alu_lanes + ((k - 1) // 2 + 2 * (k - 1) + 1) * 4, p2w,
-                  4 * packing.recompose_lanes]
+        widths = table_widths(ctx, packing)
         perms, hash_perms, hash_bytes, model_launches = workload_model(field, cpd.table_heights, widths, packing)
         kernel_ms = {kk: v[0] / prof_steps for kk, v in prof.items() if not kk.startswith("stage:")}
         stage_ms = {kk[6:]: v[0] / prof_steps for kk, v in prof.items() if kk.startswith("stage:") and not kk.startswith("stage:count:")}
@@ -1272,36 +1354,13 @@ def main():
                   file=sys.stderr)
         avg_launch_ms = hash_ms / hash_launches if hash_launches else float("nan")
         achieved = (hash_bytes / launches_per_step) / (avg_launch_ms * 1e-3) / 1e9 if hash_launches else None
-        line = {
-            "metric": "prove_next_layer ms + Poseidon2 perms/s, KoalaBear 2^20-row circuit, 1/8 GPU",
-            "value": ms_per_step,
-            "unit": "ms",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": False,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32 Montgomery (31-bit prime field, degree-4 extension); Poseidon2 hashing as exact integers in f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"prove_next_layer (verifier-circuit run on the device + prove_all_tables) of the synthetic "
-                            f"{field} 2^{log_h}-row recursion layer: tables const/public/alu/poseidon2/recompose, "
-                            f"FRI blowup 4, arity<=4, 54 queries, 15-bit PoW; circuit inputs + NextLayerPrepCache "
-                            f"resident in HBM",
-                "circuit_levels": pc.levels,
-                "field": field, "log_height": log_h, "table_heights": cpd.table_heights, "table_widths": widths,
-                "ops": dict(zip(["const", "public", "alu", "poseidon2", "recompose", "witnesses", "circuit_ops"], counts)),
-                "fri": FRI, "independent_proofs": world, "proof_bytes": proof_len,
-                "parallelism": f"{world} independent proofs, one per GPU, no data-path collective",
-            },
+        line = headline_line(args, world, ms_per_step, pc, cpd, widths, counts, last_proof, perms)
+        line.update({
             "ranks": ranks,
             # what an N-GPU run of this entry is to be compared with (the tree entry has its own: run_tree)
             # (ranks that share a GPU - the gloo run on a one-GPU box - split it: solo = step x GPUs / ranks)
             "scaling_prediction": weak_scaling_prediction(ms_per_step * max(1, ranks.get("distinct_gpus") or world) / world),
             "proof_verified": proof_verified,
-            "proof_sha256": proof_sha256,
             "proof_verify_ms": verify_ms,
             "value_incl_h2d_ms": incl_h2d_ms,
             "prep_miss_ms": prep_miss_ms,
@@ -1311,12 +1370,10 @@ def main():
             "small_layer_throughput": small_tput,
             "sustained": sustained,
             "root_handoff_ms": handoff_ms,
-            "poseidon2_perms_per_s": perms * world / (ms_per_step * 1e-3),
-            "poseidon2_perms_per_step": perms,
             "kernel_ms_per_step": kernel_ms,
             "stage_wall_ms_per_step": stage_ms,
             "dominant_kernel_family": dominant,
-        }
+        })
         # `roofline`: the dominant kernel against the roof that binds it.  MMCS leaf hashing is one Poseidon2 permutation
         # per 32 B absorbed: it is bound by VALU issue - the permutation runs in FP64 (exact integer arithmetic in
         # doubles, csrc/poseidon2_f64.hip.h), so its price is FP64 instructions per permutation x the FP64 issue rate

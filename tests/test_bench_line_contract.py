@@ -95,3 +95,41 @@ def test_detail_file_round_trip(tmp_path):
     p = tmp_path / "bench_detail.json"
     bench.write_detail(full, str(p))
     assert json.loads(p.read_text()) == full
+
+
+def _plain_line(steps=7):
+    """The line of a plain run (bench.headline_line) over stand-ins for the prepared circuit and its prover data."""
+    from types import SimpleNamespace
+    args = SimpleNamespace(field="koala-bear", log_height=20, steps=steps, warmup=2)
+    pc = SimpleNamespace(levels=57)
+    cpd = SimpleNamespace(table_heights=[1 << 20] * 5)
+    return bench.headline_line(args, 1, 27.5, pc, cpd, [4, 4, 84, 308, 4], [1, 2, 3, 4, 5, 6, 7], bytes(range(256)) * 3, 129761280)
+
+
+def test_plain_run_line_meets_the_contract():
+    """A plain run states the headline alone: the contract fields are all there, the measurements of --full are null."""
+    full = _plain_line()
+    line = json.loads(bench.contract_line(full, "bench_detail.json"))
+    assert REQUIRED <= set(line), REQUIRED - set(line)
+    assert line["value"] == line["ms_per_step"] == 27.5 and line["steps"] == 7 and line["warmup"] == 2
+    assert line["unit"] == "ms" and line["higher_is_better"] is False
+    assert line["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["proof_verified"] is None
+    assert line["proof_sha256"] == __import__("hashlib").sha256(bytes(range(256)) * 3).hexdigest()
+    assert line["config"]["proof_bytes"] == 768
+    assert line["poseidon2_perms_per_s"] == pytest.approx(129761280 / 27.5e-3, rel=1e-5)
+
+
+def test_dump_outputs_float32_exact_and_bounded(tmp_path, monkeypatch):
+    import numpy as np
+    proof = np.frombuffer(bytes(range(256)) * 5, dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "out"), {"proof": proof})
+    got = np.load(tmp_path / "out" / "proof.npy")
+    assert got.dtype == np.float32 and np.array_equal(got.astype(np.uint8), proof)
+    # beyond the budget: a fixed, seeded sample, the same from run to run
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 400)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": np.arange(1000), "y": np.arange(10)})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.nbytes <= 200 and np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "y.npy"), np.arange(10))

@@ -180,7 +180,7 @@ def test_plain_bench_entry_launches_its_own_ranks():
     env = dict(os.environ, P3R_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-height", "12",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-height", "12", "--full",
            "--no-cpu-baseline", "--no-config2", "--no-small-layers"]
     out = subprocess.run(cmd + ["--detail-out", DETAIL], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -220,7 +220,7 @@ def test_default_bench_line_two_ranks_over_gloo():
     env = dict(os.environ, P3R_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-height", "12",
-           "--no-cpu-baseline", "--no-config2", "--no-small-layers"]
+           "--full", "--no-cpu-baseline", "--no-config2", "--no-small-layers"]
     out = subprocess.run(cmd + ["--detail-out", DETAIL], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = bench_result(out)
@@ -238,8 +238,8 @@ def test_rccl_process_group_of_one(launcher):
     Nothing about scaling is claimed."""
     env = {k: v for k, v in os.environ.items() if k not in ("P3R_BENCH_BACKEND", "RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    args = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-height", "12", "--no-cpu-baseline",
-            "--no-small-layers", "--force-dist"]
+    args = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-height", "12", "--full", "--no-cpu-baseline",
+            "--no-config2", "--no-quintic", "--no-small-layers", "--force-dist"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
                "--master-port", str(free_port())] + args

@@ -1,0 +1,32 @@
+"""GPU: the plain bench.py run - headline only, --steps timed steps, and --dump-outputs writing the last timed proof,
+the same bytes from run to run (the inputs are fixed by the arguments)."""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_timed_proof(tmp_path):
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-height", "12",
+               "--dump-outputs", str(out_dir), "--detail-out", str(tmp_path / f"detail_{run}.json")]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+        assert line["ms_per_step"] > 0 and line["value"] == line["ms_per_step"] and line["unit"] == "ms"
+        assert line["roofline"] is None and line["cpu_baseline"] is None   # measurements of --full
+        proof = np.load(out_dir / "proof.npy")
+        assert proof.dtype == np.float32 and proof.size == line["config"]["proof_bytes"]
+        assert hashlib.sha256(proof.astype(np.uint8).tobytes()).hexdigest() == line["proof_sha256"]
+        dumps.append(proof)
+    assert np.array_equal(dumps[0], dumps[1])

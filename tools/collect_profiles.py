@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the raw output of tools/profile_round.sh (gpurun_out/final/) into the committed summaries
+"""Turn the raw output of tools/profile_round.sh ($P3R_PROFILE_RAW, default profile_raw/) into the committed summaries
 under profiles/<round>/: the bench line, rocprofv3's kernel stats, the per-kernel PMC traffic and SQ
 instruction counters, the microbenchmark outputs.   usage: python tools/collect_profiles.py r02"""
 import collections
@@ -13,7 +13,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROUND = next((a for a in sys.argv[1:] if not a.startswith("--")), "r05")
-SRC, OUT = os.path.join(ROOT, "gpurun_out", "final"), os.path.join(ROOT, "profiles", ROUND)
+SRC, OUT = os.path.join(ROOT, os.environ.get("P3R_PROFILE_RAW", "profile_raw")), os.path.join(ROOT, "profiles", ROUND)
 os.makedirs(OUT, exist_ok=True)
 
 
@@ -116,7 +116,7 @@ kern = {k: {"launches": len(fe.get(k, [])),
             "write_kb_per_launch": sum(wr.get(k, [0])) / max(len(wr.get(k, [])), 1)} for k in sorted(set(fe) | set(wr))}
 json.dump({
     "provenance": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over "
-                  "`python3 bench.py --no-cpu-baseline --no-config2 --no-small-layers --steps 1 --warmup 0` "
+                  "`python3 bench.py --full --no-cpu-baseline --no-config2 --no-small-layers --no-quintic --steps 1 --warmup 0` "
                   "(tools/profile_round.sh), MI355X, round %s; counter unit KB; averages over every launch of the "
                   "kernel in the run, except k_mmcs_hash_rows: without the preprocessed commit of the preparation" % ROUND,
     "note": "raw counter values. gfx950 tallies the 128-B requests of a coalesced streaming read at 64 B, so FETCH_SIZE is "
