@@ -167,8 +167,8 @@ inline std::shared_ptr<DevPool>& tls_pool() {
   return p;
 }
 
-// Development knobs (tile sizes, the pre-round-2 NTT passes, copy-engine fetches, Merkle partition): environment
-// variables that select equality-tested alternatives of the shipped path.  They exist in the `knobs` build of the
+// Development knobs (tile sizes, the Merkle partition, the test seam of the width-32 diagonal): environment variables
+// that choose values inside the shipped path, each equality-tested.  They exist in the `knobs` build of the
 // library only (-DP3R_TUNING_KNOBS: plonky3_recursion_amd/knobs/libp3r_hip.so, what tests/test_gpu_cpp_host.py and the
 // tuning tools load); in the product build every knob reads as unset and the alternatives are dead code the
 // compiler drops.
@@ -221,8 +221,7 @@ inline hipError_t copy_sync(hipStream_t s, void* dst, const void* src, size_t by
 // Fills and small copies of the proof path as kernels of our own instead of hipMemsetAsync / hipMemcpyAsync: the runtime's
 // blit path costs more on the host per call than a kernel launch, which shows where the GPU has nothing queued - the first
 // operation after a transcript round trip, the dozen memsets that open a circuit run.  Same-box A/B
-// (profiles/r06/host_gaps.txt): headline 27.16 -> 27.07 ms, 2^16-row layer 4.09 -> 3.92 ms.  P3R_RUNTIME_COPIES=1 (knobs
-// build) restores the runtime calls.
+// (profiles/r06/host_gaps.txt): headline 27.16 -> 27.07 ms, 2^16-row layer 4.09 -> 3.92 ms.
 static __global__ void __launch_bounds__(256) k_fill_bytes(uint8_t* __restrict__ p, uint32_t pattern, size_t n) {
   const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nt = (size_t)gridDim.x * 256;
   const size_t mis = (16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15, head = mis < n ? mis : n;
@@ -244,14 +243,9 @@ static __global__ void __launch_bounds__(256) k_copy_small(uint8_t* __restrict__
   const size_t done = nq * sizeof(T);
   if (tid < n - done) dst[done + tid] = src[done + tid];
 }
-inline bool runtime_copies() {
-  static const bool on = tuning_knob("P3R_RUNTIME_COPIES") != nullptr;
-  return on;
-}
 inline hipError_t fill_async(hipStream_t s, void* p, int byte, size_t bytes) {
   if (bytes == 0) return hipSuccess;
   host_mark("launch: fill");
-  if (runtime_copies()) return hipMemsetAsync(p, byte, bytes, s);
   const uint32_t b = (uint32_t)byte & 0xFFu, pattern = b * 0x01010101u;
   const size_t blocks = std::min<size_t>((bytes / 16 + 255) / 256 + 1, 4096);
   hipLaunchKernelGGL(k_fill_bytes, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<uint8_t*>(p), pattern, bytes);
@@ -317,8 +311,7 @@ struct HostStage {
     }
     std::memcpy(base + off, src, bytes);
     // (the launch publishes the host's stores: the ring is coherent memory, read over the link by one small kernel)
-    hipError_t e = runtime_copies() ? hipMemcpyAsync(dst, base + off, bytes, hipMemcpyHostToDevice, s)
-                                    : copy_async_kernel(s, dst, base_dev + off, bytes);
+    hipError_t e = copy_async_kernel(s, dst, base_dev + off, bytes);
     off += need;
     return e;
   }
@@ -389,10 +382,6 @@ struct HostPost {
   ~HostPost() {
     if (host) (void)hipHostFree(host);
   }
-  static bool enabled() {
-    static const bool off = tuning_knob("P3R_NO_POLLED_FETCH") != nullptr;
-    return !off;
-  }
   // `words` <= kWords cells from `src` (device) -> *out (valid until the next post)
   hipError_t post(hipStream_t s, const uint32_t* src, size_t words, const uint32_t** out) {
     if (!host) {
@@ -420,12 +409,11 @@ struct HostPost {
     // The k-th round trip of a proof takes what it took in the proof before (same shape, same kernels): sleep through
     // most of THAT, then poll awake.  A wait that outlasts its prediction (another shape, sibling provers on the GPU)
     // falls back to naps; the first proof of a shape has no prediction and naps as before.
-    static const int mode = tuning_knob("P3R_POST_MODE") ? atoi(tuning_knob("P3R_POST_MODE")) : 0;  // 1: naps only, 2: spin only
     const int sl = slot < kSlots ? slot : kSlots - 1;
     if (in_proof) ++slot;
     const auto t0 = std::chrono::steady_clock::now();
     auto elapsed_ns = [&] { return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); };
-    const int64_t expect = mode == 0 && in_proof ? expect_ns[sl] : 0;
+    const int64_t expect = in_proof ? expect_ns[sl] : 0;
     if (expect > 400000) {
       // asleep for the first three quarters (in pieces, so that a result that comes early is not slept through for long)
       const int64_t until = expect - std::max<int64_t>(expect / 4, 200000);
@@ -435,7 +423,7 @@ struct HostPost {
     const int64_t awake_until = expect > 400000 ? expect + expect / 2 + 500000 : 0;   // then: naps
     for (uint64_t spins = 0;; ++spins) {
       if (*flag == seq) break;
-      if (mode != 2 && spins > (uint64_t(1) << 14) && (spins & 0x3F) == 0x3F) {
+      if (spins > (uint64_t(1) << 14) && (spins & 0x3F) == 0x3F) {
         if (awake_until && elapsed_ns() < awake_until) std::this_thread::yield();
         else if (spins > (uint64_t(1) << 17)) std::this_thread::sleep_for(std::chrono::microseconds(20));
         else std::this_thread::yield();
@@ -555,12 +543,7 @@ struct p3r_ctx {
   std::string cur_stage;
   double cur_stage_t0 = 0;
   int partial_rounds = 0;
-  hipStream_t stream = nullptr;
-  // second stream of the commits (prove_impl.hip.h::lde_and_commit): the leaf hashing of one height class runs on it
-  // while the main stream extends the next class; joined before the Merkle levels.  Nothing else uses it.
-  hipStream_t stream2 = nullptr;
-  hipStream_t stream2_low = nullptr;   // the same at the lowest priority (A/B: P3R_COMMIT_OVERLAP_MODE = 2)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipStream_t stream = nullptr;  // the context's one stream: everything it does is ordered on it
   int n_cus = 256;  // compute units of the device (grids of the persistent kernels)
   p3r::DevBuf rc;  // Poseidon2 constants, Montgomery
   p3r::DevBuf rc_f64;  // the same constants as canonical doubles (poseidon2_f64.hip.h)
@@ -596,7 +579,7 @@ struct p3r_ctx {
 // `words` cells from device memory into `dst` (host), for results the host transcript waits on.
 inline hipError_t fetch_small(p3r_ctx* ctx, const uint32_t* src, size_t words, uint32_t* dst) {
   if (words == 0) return hipSuccess;
-  if (p3r::HostPost::enabled() && words <= p3r::HostPost::kWords) {
+  if (words <= p3r::HostPost::kWords) {
     const uint32_t* got = nullptr;
     p3r::host_mark("fetch: posted, waiting for the GPU");
     hipError_t e = ctx->post.post(ctx->stream, src, words, &got);

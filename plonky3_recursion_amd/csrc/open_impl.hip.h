@@ -109,7 +109,7 @@ struct Opener {
     // kernel and polled for - the copy engine's round trip is 30 - 40 us longer (profiles/r06/host_gaps.txt); read in
     // place, before the next post
     const uint32_t* raw = nullptr;
-    if (HostPost::enabled() && used * DC <= HostPost::kWords) P3R_HIP(ctx->post.post(ctx->stream, out.p, used * DC, &raw));
+    if (used * DC <= HostPost::kWords) P3R_HIP(ctx->post.post(ctx->stream, out.p, used * DC, &raw));
     else P3R_HIP(ctx->landing.fetch(ctx->stream, out.p, used * DC * 4, &raw));
     keep.clear();  // `out` stays for the reduced openings (values_dev)
     std::vector<std::vector<std::vector<E>>> res(jobs.size());

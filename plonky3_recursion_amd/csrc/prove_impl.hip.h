@@ -85,11 +85,7 @@ inline ZkKey zk_key_of(const p3r_ctx* ctx, uint64_t nonce) {
   return k;
 }
 
-// the tiled fills of kernels_zk.hip.h (one ChaCha block per eight cells); P3R_ZK_CELL_FILL=1 (knobs build): the per-cell kernels
-inline bool zk_cell_fill() {
-  static const bool on = tuning_knob("P3R_ZK_CELL_FILL") != nullptr;
-  return on;
-}
+// the tiled fills of kernels_zk.hip.h (one ChaCha block per eight cells)
 template <class PP>
 void launch_zk_tiles(p3r_ctx* ctx, std::vector<ZkTileJob>& jobs, const ZkKey& key, const char* family) {
   uint64_t blocks = 0;
@@ -114,139 +110,52 @@ template <class PP>
 std::vector<std::unique_ptr<p3r_dmat>> draw_salts(p3r_ctx* ctx, const std::vector<const p3r_dmat*>& mats, int salt_round, const ZkKey& key) {
   const uint32_t S = ctx->cfg.mmcs_salt_elems;
   std::vector<std::unique_ptr<p3r_dmat>> out;
-  if (!zk_cell_fill()) {
-    std::vector<ZkTileJob> tj;
-    for (size_t i = 0; i < mats.size(); ++i) {
-      out.push_back(dmat_alloc(mats[i]->h, S));
-      ZkTileJob j{};
-      j.dst = out.back()->d; j.rows = mats[i]->h; j.w2 = S; j.mode = 1; j.stride = 1;
-      j.stream = zk_stream_id(salt_round, i);
-      tj.push_back(j);
-    }
-    launch_zk_tiles<PP>(ctx, tj, key, "mmcs_salts");
-    return out;
-  }
-  std::vector<ZkSaltJob> jobs;
-  uint64_t blocks = 0;
+  std::vector<ZkTileJob> tj;
   for (size_t i = 0; i < mats.size(); ++i) {
     out.push_back(dmat_alloc(mats[i]->h, S));
-    ZkSaltJob j{};
-    j.dst = out.back()->d; j.h = mats[i]->h; j.S = S; j.stride = 1;
+    ZkTileJob j{};
+    j.dst = out.back()->d; j.rows = mats[i]->h; j.w2 = S; j.mode = 1; j.stride = 1;
     j.stream = zk_stream_id(salt_round, i);
-    j.block0 = (uint32_t)blocks;
-    blocks += (uint64_t)S * ((j.h + kBlock - 1) / kBlock);
-    jobs.push_back(j);
+    tj.push_back(j);
   }
-  if (blocks >= (uint64_t(1) << 31)) fail(P3R_EUNSUPPORTED, "salt launch of %llu tiles", (unsigned long long)blocks);
-  DevBuf d_jobs((jobs.size() * sizeof(ZkSaltJob) + 3) / 4);
-  P3R_HIP(ctx->stage.upload(ctx->stream, d_jobs.p, jobs.data(), jobs.size() * sizeof(ZkSaltJob)));
-  ProfScope ps(ctx, "mmcs_salts");
-  hipLaunchKernelGGL(k_zk_salts<PP>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, reinterpret_cast<const ZkSaltJob*>(d_jobs.p),
-                     (int)jobs.size(), key);
-  P3R_HIP(hipGetLastError());
+  launch_zk_tiles<PP>(ctx, tj, key, "mmcs_salts");
   return out;
 }
 
 // `salt_round` >= 0 under a hiding MMCS (p3r_config.mmcs_salt_elems > 0): the stream round of this batch's salts.
 template <class PP>
 std::unique_ptr<p3r_tree> commit_dmats(p3r_ctx* ctx, const std::vector<const p3r_dmat*>& mats,
-                                       std::vector<uint32_t>& cap_mont, std::map<size_t, DevBuf>* pre = nullptr,
-                                       int salt_round = -1, const ZkKey* key = nullptr) {
+                                       std::vector<uint32_t>& cap_mont, int salt_round = -1, const ZkKey* key = nullptr) {
   auto tree = std::make_unique<p3r_tree>();
   tree->mats = mats;
   if (ctx->cfg.mmcs_salt_elems) {
     if (salt_round < 0 || !key) fail(P3R_EHIP, "internal: a commit without its salt stream under a hiding MMCS");
-    if (pre && !pre->empty()) fail(P3R_EHIP, "internal: pre-hashed classes under a hiding MMCS");
     tree->salt_elems = (int)ctx->cfg.mmcs_salt_elems;
     tree->salt_owned = draw_salts<PP>(ctx, mats, salt_round, *key);
     tree->mats.clear();
     for (size_t i = 0; i < mats.size(); ++i) { tree->mats.push_back(mats[i]); tree->mats.push_back(tree->salt_owned[i].get()); }
   }
   std::vector<uint32_t> cap_canon((size_t)P2_DIGEST << ctx->cfg.cap_height);
-  mmcs_commit<PP>(ctx, tree.get(), cap_canon.data(), pre);
+  mmcs_commit<PP>(ctx, tree.get(), cap_canon.data());
   cap_mont.resize(cap_canon.size());
   for (size_t i = 0; i < cap_canon.size(); ++i) cap_mont[i] = Fp<PP>::from_canonical(cap_canon[i]).v;
   return tree;
 }
 
-// Coset LDE + MMCS commitment of one round's matrices (TwoAdicFriPcs::commit).  The product runs them back to back on the
-// ctx's stream.  The `knobs` build can take the leaf hashing of ONE height class off the critical path instead
-// (P3R_COMMIT_OVERLAP=1): the class with the most permutations is extended first and hashed on the ctx's second stream
-// while the main stream extends the other classes - the hash is VALU-bound (0.96 busy), the LDE passes leave a third of
-// their time to memory phases.  Measured (profiles/r05/commit_overlap_ab.txt): between two contexts the pair gains
-// 0.55 ms of a 1.9 ms LDE, inside the prover 0.0 - 0.2 ms of 28 (paired, 40 proofs per form alternating in one
-// process): below the 0.3 ms a change has to earn, so it is not the product's path.  Same digests, same tree, same bytes
-// (tests/test_gpu_cpp_host.py::test_two_stream_commit_gives_the_same_proof).
+// Coset LDE + MMCS commitment of one round's matrices (TwoAdicFriPcs::commit), back to back on the ctx's one stream
+// (a second stream for the leaf hashing gained too little: profiles/r05/commit_overlap_ab.txt).
 template <class PP>
 std::unique_ptr<p3r_tree> lde_and_commit(p3r_ctx* ctx, const std::vector<LdeItem>& items, int log_blowup,
                                          std::vector<std::unique_ptr<p3r_dmat>>& ldes, std::vector<uint32_t>& cap_mont,
                                          int salt_round = -1, const ZkKey* key = nullptr) {
-  // (read per call, not once: tools/ab_commit_overlap.py alternates the forms proof by proof inside one process)
-  const bool off = tuning_knob("P3R_COMMIT_OVERLAP") == nullptr;
-  // A/B forms (knobs build): 1 = the same split of the LDE and of the hash launch on ONE stream (what the split costs by
-  // itself), 2 = the hash on a lowest-priority stream (the LDE's workgroups go first wherever both are waiting)
-  const int mode = tuning_knob("P3R_COMMIT_OVERLAP_MODE") ? atoi(tuning_knob("P3R_COMMIT_OVERLAP_MODE")) : 0;
-  std::map<size_t, uint64_t> perms, cells;   // per height class of the LDEs
-  for (auto& it : items) {
-    cells[it.in->h] += (uint64_t)it.in->h * it.in->w;
-    perms[it.in->h] += it.in->w;             // columns for now
-  }
-  size_t pick = 0;
-  uint64_t best = 0, total_cells = 0;
-  for (auto& kv : perms) {
-    kv.second = (uint64_t)kv.first * ((kv.second + P2_RATE - 1) / P2_RATE);
-    if (kv.second > best) { best = kv.second; pick = kv.first; }
-    total_cells += cells[kv.first];
-  }
-  const bool overlap = !off && !ctx->prof_enabled && ctx->cfg.mmcs_arity != 4 && !ctx->cfg.mmcs_salt_elems && perms.size() >= 2 &&
-                       total_cells - cells[pick] >= (uint64_t(1) << 22) && best >= (uint64_t(1) << 20);
   ldes.clear();
   ldes.resize(items.size());
   std::vector<const p3r_dmat*> ptrs(items.size());
-  if (!overlap) {
-    host_mark("lde: enqueue");
-    auto out = coset_lde_batch<PP>(ctx, items, log_blowup);
-    host_mark("lde: enqueued; commit: enqueue");
-    for (size_t i = 0; i < items.size(); ++i) { ldes[i] = std::move(out[i]); ptrs[i] = ldes[i].get(); }
-    return commit_dmats<PP>(ctx, ptrs, cap_mont, nullptr, salt_round, key);
-  }
-  std::vector<LdeItem> first, rest;
-  std::vector<size_t> first_at, rest_at;
-  for (size_t i = 0; i < items.size(); ++i) {
-    (items[i].in->h == pick ? first : rest).push_back(items[i]);
-    (items[i].in->h == pick ? first_at : rest_at).push_back(i);
-  }
-  {
-    auto out = coset_lde_batch<PP>(ctx, first, log_blowup);
-    for (size_t k = 0; k < first.size(); ++k) { ldes[first_at[k]] = std::move(out[k]); ptrs[first_at[k]] = ldes[first_at[k]].get(); }
-  }
-  std::map<size_t, DevBuf> pre;
-  // `pre` is written by the side stream: an exception below must not release it while that kernel still runs
-  struct DrainSideStream {
-    p3r_ctx* ctx;
-    bool armed = false;
-    ~DrainSideStream() {
-      if (!armed) return;
-      if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-      if (ctx->stream2_low) (void)hipStreamSynchronize(ctx->stream2_low);
-    }
-  } drain_on_unwind{ctx};
-  {
-    std::vector<const p3r_dmat*> cls;   // commit order within the class = the caller's order (stable)
-    for (size_t i : first_at) cls.push_back(ptrs[i]);
-    const size_t h = cls[0]->h;
-    uint32_t* dig = pre.emplace(h, DevBuf(P2_DIGEST * h)).first->second.p;
-    hash_rows<PP>(ctx, {cls}, {dig}, /*side=*/mode == 1 ? 0 : mode == 2 ? 2 : 1);
-    drain_on_unwind.armed = mode != 1;
-  }
-  {
-    auto out = coset_lde_batch<PP>(ctx, rest, log_blowup);
-    for (size_t k = 0; k < rest.size(); ++k) { ldes[rest_at[k]] = std::move(out[k]); ptrs[rest_at[k]] = ldes[rest_at[k]].get(); }
-  }
-  if (mode != 1) hash_rows_join(ctx);
-  auto tree = commit_dmats<PP>(ctx, ptrs, cap_mont, &pre);
-  drain_on_unwind.armed = false;   // joined on the main stream: `pre` is released in stream order from here on
-  return tree;
+  host_mark("lde: enqueue");
+  auto out = coset_lde_batch<PP>(ctx, items, log_blowup);
+  host_mark("lde: enqueued; commit: enqueue");
+  for (size_t i = 0; i < items.size(); ++i) { ldes[i] = std::move(out[i]); ptrs[i] = ldes[i].get(); }
+  return commit_dmats<PP>(ctx, ptrs, cap_mont, salt_round, key);
 }
 
 // Proof-of-work grinding on the device: the smallest witness w such that, after observing w, the
@@ -312,7 +221,7 @@ std::vector<std::unique_ptr<p3r_dmat>> zk_randomize(p3r_ctx* ctx, const std::vec
   }
   if (blocks >= (uint64_t(1) << 31)) fail(P3R_EUNSUPPORTED, "ZK randomisation launch of %llu tiles", (unsigned long long)blocks);
   if (jobs.empty()) return out;
-  if (!zk_cell_fill() && !zero_fill) {   // (a zero fill draws nothing: the per-cell kernel is the cheap one there)
+  if (!zero_fill) {   // (a zero fill draws nothing: the per-cell kernel is the cheap one there)
     std::vector<ZkTileJob> tj;
     for (auto& j : jobs) {
       ZkTileJob t{};
@@ -389,7 +298,7 @@ std::unique_ptr<p3r_prep> prep_create(p3r_ctx* ctx, const p3r_air_desc* airs, co
   {
     // a hiding MMCS salts the preprocessed commitment too; it is made once per circuit: the nonce of `proof 0`
     const ZkKey prep_key = zk_key_of(ctx, 0);
-    prep->tree = commit_dmats<PP>(ctx, ptrs, cap_mont, nullptr, kSaltRound + ZK_ROUND_PREP, &prep_key);
+    prep->tree = commit_dmats<PP>(ctx, ptrs, cap_mont, kSaltRound + ZK_ROUND_PREP, &prep_key);
   }
   prep->cap_canonical.resize(cap_mont.size());
   for (size_t i = 0; i < cap_mont.size(); ++i) prep->cap_canonical[i] = F::raw(cap_mont[i]).to_canonical();
@@ -732,7 +641,7 @@ std::vector<uint8_t> prove_batch(p3r_ctx* ctx, const p3r_prep* prep, const p3r_d
   }
   ptrs.clear();
   for (auto& ck : chunks) ptrs.push_back(ck.lde.get());
-  auto quot_tree = commit_dmats<PP>(ctx, ptrs, quot_cap, nullptr, kSaltRound + ZK_ROUND_QUOTIENT, &zk_key);
+  auto quot_tree = commit_dmats<PP>(ctx, ptrs, quot_cap, kSaltRound + ZK_ROUND_QUOTIENT, &zk_key);
   for (uint32_t v : quot_cap) ch.observe(F::raw(v));
   // ZK: the random round - per instance a fully random matrix of Challenge::DIMENSION (+ R) columns over the extended
   // trace domain, opened at zeta; its commitment is observed after the quotient's (batch_stark.rs:623-625)
@@ -749,7 +658,7 @@ std::vector<uint8_t> prove_batch(p3r_ctx* ctx, const p3r_prep* prep, const p3r_d
     rand_lde = coset_lde_batch<PP>(ctx, lde_items, log_blowup);
     ptrs.clear();
     for (auto& m : rand_lde) ptrs.push_back(m.get());
-    rand_tree = commit_dmats<PP>(ctx, ptrs, rand_cap, nullptr, kSaltRound + ZK_ROUND_RANDOM, &zk_key);
+    rand_tree = commit_dmats<PP>(ctx, ptrs, rand_cap, kSaltRound + ZK_ROUND_RANDOM, &zk_key);
     for (uint32_t v : rand_cap) ch.observe(F::raw(v));
   }
   const E zeta = ch.sample_ext();
@@ -1020,22 +929,10 @@ std::vector<uint8_t> prove_batch(p3r_ctx* ctx, const p3r_prep* prep, const p3r_d
         p3r_tree& T = *ph.tree;
         T.salt_elems = (int)S; T.phase_salt_stride = arity; T.phase_rows = rows;
         T.phase_salts.alloc((size_t)S * n_in);
-        ZkSaltJob j{};
-        j.dst = T.phase_salts.p; j.h = rows; j.S = S; j.stride = (uint32_t)arity;
-        j.stream = zk_stream_id(kSaltRoundFri, phases.size());
-        j.block0 = 0;
-        DevBuf d_job((sizeof(ZkSaltJob) + 3) / 4);
-        if (!zk_cell_fill()) {
-          std::vector<ZkTileJob> tj(1);
-          tj[0].dst = j.dst; tj[0].rows = rows; tj[0].w2 = S; tj[0].mode = 1; tj[0].stride = (uint32_t)arity; tj[0].stream = j.stream;
-          launch_zk_tiles<PP>(ctx, tj, zk_key, "mmcs_salts");
-        } else {
-          P3R_HIP(ctx->stage.upload(ctx->stream, d_job.p, &j, sizeof j));
-          ProfScope ps(ctx, "mmcs_salts");
-          hipLaunchKernelGGL(k_zk_salts<PP>, dim3((unsigned)(S * ((rows + kBlock - 1) / kBlock))), dim3(kBlock), 0, ctx->stream,
-                             reinterpret_cast<const ZkSaltJob*>(d_job.p), 1, zk_key);
-        }
-        P3R_HIP(hipGetLastError());
+        std::vector<ZkTileJob> tj(1);
+        tj[0].dst = T.phase_salts.p; tj[0].rows = rows; tj[0].w2 = S; tj[0].mode = 1; tj[0].stride = (uint32_t)arity;
+        tj[0].stream = zk_stream_id(kSaltRoundFri, phases.size());
+        launch_zk_tiles<PP>(ctx, tj, zk_key, "mmcs_salts");
         for (uint32_t c = 0; c < S; ++c) cols.push_back(T.phase_salts.p + (size_t)c * n_in);
       }
       const uint32_t* const* dcols = col_table(ctx, cols);

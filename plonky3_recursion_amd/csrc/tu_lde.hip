@@ -158,8 +158,7 @@ constexpr int kNtt2MinLogR = 5, kNtt2MaxLogR = 12, kNtt2MaxLineLogR = 13;
 // layer): one launch of the mixed-size kernel instead of one per size.
 template <class JOB>
 bool merge_small_launches(std::map<int, std::pair<std::vector<JOB>, uint64_t>>& by_r, std::vector<JOB>& all, uint32_t& blocks) {
-  static const bool off = tuning_knob("P3R_NTT_NO_MIXED") != nullptr;
-  if (off || by_r.size() < 2) return false;
+  if (by_r.size() < 2) return false;
   uint64_t total = 0;
   for (auto& kv : by_r) {
     if (kv.first & 1) return false;  // a 2^14-cell column tile / a 2^13-cell line tile: own launch
@@ -266,7 +265,6 @@ std::vector<std::unique_ptr<p3r_dmat>> coset_lde_batch(p3r_ctx* ctx, const std::
   std::map<int, std::pair<std::vector<NttColJob>, uint64_t>> fwd_col;    // sub-transform size -> (jobs, blocks)
   std::map<int, std::pair<std::vector<NttLineJob>, uint64_t>> fwd_line;
   std::map<int, std::pair<std::vector<NttColJob>, uint64_t>> inv1, inv2;
-  static const bool lean_fwd = !tuning_knob("P3R_NTT_OLD");
   static const int fwd_la_cap = tuning_knob("P3R_NTT_FWD_LOG_N1") ? atoi(tuning_knob("P3R_NTT_FWD_LOG_N1")) : 8;
   for (const LdeItem& it : items) {
     const p3r_dmat* in = it.in;
@@ -306,7 +304,7 @@ std::vector<std::unique_ptr<p3r_dmat>> coset_lde_batch(p3r_ctx* ctx, const std::
     scratch.emplace_back(N * w);
     uint32_t* tmp = scratch.back().p;
     auto tw4i = get_tw4<PP>(ctx, log_n, 1);
-    const bool lean_inv = lean_fwd && la >= kNtt2MinLogR && lb <= kNtt2MaxLogR && la >= kNtt2LogTile - lb && lb >= kNtt2LogTile - la;
+    const bool lean_inv = la >= kNtt2MinLogR && lb <= kNtt2MaxLogR && la >= kNtt2LogTile - lb && lb >= kNtt2LogTile - la;
     if (lean_inv) {
       NttColJob j1{};
       j1.in = in->d; j1.out = tmp;
@@ -352,17 +350,15 @@ std::vector<std::unique_ptr<p3r_dmat>> coset_lde_batch(p3r_ctx* ctx, const std::
     // forward pass 1 (all cosets): scale by s_z^k, size-N1 transforms along n1, twiddle, in place rows.
     // The forward transform has its own split: its strided pass wants few rows per tile (long
     // contiguous segments per row), its second pass is contiguous whatever N2 is.
-    // (measured: 2^8 x 2^12 beats 2^10 x 2^10 at n = 2^20; past 2^12 contiguous points per line the
-    // balanced split is better again)
-    // With the lean kernels the contiguous pass takes lines of up to 2^13 cells (one tile), so the strided
-    // pass keeps 2^8 rows (128-byte segments) up to 2^21 rows and grows only beyond that (2^22: 2^9 rows,
-    // 64-byte segments; the balanced 2^11 x 2^11 split moved 16-byte segments).
-    const int la_f = lean_fwd ? std::max(std::min(log_n / 2, fwd_la_cap), log_n - kNtt2MaxLineLogR)
-                              : (log_n - fwd_la_cap <= 12 ? std::min(log_n / 2, fwd_la_cap) : log_n / 2);
+    // (measured: 2^8 x 2^12 beats 2^10 x 2^10 at n = 2^20)
+    // The lean kernels' contiguous pass takes lines of up to 2^13 cells (one tile), so the strided pass keeps
+    // 2^8 rows (128-byte segments) up to 2^21 rows and grows only beyond that (2^22: 2^9 rows, 64-byte
+    // segments; the balanced 2^11 x 2^11 split moved 16-byte segments).
+    const int la_f = std::max(std::min(log_n / 2, fwd_la_cap), log_n - kNtt2MaxLineLogR);
     const int lb_f = log_n - la_f;
     auto pre = get_pre<PP>(ctx, log_n, la_f, lb_f, added_bits, shift);
     auto tw4f = get_tw4<PP>(ctx, log_n, 0);
-    if (lean_fwd && la_f >= kNtt2MinLogR && la_f <= kNtt2MaxLogR && lb_f >= kNtt2MinLogR && lb_f <= kNtt2MaxLineLogR &&
+    if (la_f >= kNtt2MinLogR && la_f <= kNtt2MaxLogR && lb_f >= kNtt2MinLogR && lb_f <= kNtt2MaxLineLogR &&
         lb_f >= kNtt2LogTile - la_f) {
       // lean kernels (kernels_ntt2.hip.h): the same two passes with compile-time geometry
       NttColJob cj{};
@@ -378,9 +374,8 @@ std::vector<std::unique_ptr<p3r_dmat>> coset_lde_batch(p3r_ctx* ctx, const std::
       auto& fc = fwd_col[la_f * 2 + bigf];
       cj.block0 = (uint32_t)fc.second;
       {
-        static const bool no_xcd = tuning_knob("P3R_NTT_NO_XCD_MAP") != nullptr;
         const uint64_t tiles = (uint64_t)w << (lb_f - (kNtt2LogTile + bigf - la_f));
-        cj.xcd_map = (!no_xcd && added_bits > 0 && (cj.block0 & 7) == 0 && (tiles & 7) == 0) ? 1 : 0;
+        cj.xcd_map = (added_bits > 0 && (cj.block0 & 7) == 0 && (tiles & 7) == 0) ? 1 : 0;
       }
       fc.second += (uint64_t)w << (lb_f - (kNtt2LogTile + bigf - la_f) + added_bits);
       fc.first.push_back(cj);

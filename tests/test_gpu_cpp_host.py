@@ -127,10 +127,9 @@ def test_cpp_host_zk_layer(oracle, tmp_path):
 
 def test_fallback_paths_give_the_same_proof(tmp_path):
     """The tuning knobs exist in the `knobs` build of the library only (plonky3_recursion_amd/knobs/libp3r_hip.so,
-    -DP3R_TUNING_KNOBS; the product build compiles them out).  The paths they select (copy-engine fetches instead
-    of polled ones, one NTT launch per sub-transform size, 256-digest Merkle workgroups, 2^13-cell line tiles, the
-    pre-round-2 NTT passes) must stay byte-identical to the product's proof; in the product build the same
-    variables change nothing."""
+    -DP3R_TUNING_KNOBS; the product build compiles them out).  The values they select (2^13-cell line tiles, one
+    forward line launch per sub-transform size, 256-digest Merkle workgroups, other lane-cooperative bounds) must keep
+    the product's proof byte for byte; in the product build the same variables change nothing."""
     if not os.path.exists(EXE):
         subprocess.run(["make", "-C", os.path.join(ROOT, "examples")], check=True)
     knobs_dir = os.path.join(ROOT, "plonky3_recursion_amd", "knobs")
@@ -147,13 +146,11 @@ def test_fallback_paths_give_the_same_proof(tmp_path):
         return open(out_file, "rb").read()
 
     want = proof("product", knobs=False)
-    assert proof("product_ignores_knobs", knobs=False, P3R_NTT_OLD="1", P3R_NO_POLLED_FETCH="1") == want
+    assert proof("product_ignores_knobs", knobs=False, P3R_NTT_LINE_LOG_TILE="13", P3R_SUBTREE_NODES="256") == want
     assert proof("default") == want
-    assert proof("unpolled", P3R_NO_POLLED_FETCH="1") == want
-    assert proof("unmixed", P3R_NTT_NO_MIXED="1", P3R_NTT_LINE_LOG_TILE="13") == want
+    assert proof("line_tiles_13", P3R_NTT_LINE_LOG_TILE="13") == want
     assert proof("wide_subtrees", P3R_SUBTREE_NODES="256", P3R_COOP_MAX_NODES="32768",
                  P3R_COOP_MAX_LEAF_ROWS="32768") == want
-    assert proof("old_ntt", P3R_NTT_OLD="1") == want
 
 
 def test_both_width32_kernel_instances_give_the_same_proof(tmp_path):
@@ -180,33 +177,3 @@ def test_both_width32_kernel_instances_give_the_same_proof(tmp_path):
     for field in ("koala-bear", "baby-bear"):
         assert got[("product", field)] == got[("knobs_builtin", field)] == got[("knobs_general", field)], field
 
-
-def test_two_stream_commit_gives_the_same_proof(tmp_path):
-    """The knobs build can hash one height class of each commit on a second stream while the main stream extends the next
-    (prove_impl.hip.h::lde_and_commit, P3R_COMMIT_OVERLAP; measured, not the product's path: profiles/r05/
-    commit_overlap_ab.txt): same bytes in every form, with and without ZK commitments."""
-    import hashlib
-    import sys
-    knobs_lib = os.path.join(ROOT, "plonky3_recursion_amd", "knobs", "libp3r_hip.so")
-    if not os.path.exists(knobs_lib):
-        pytest.skip("knobs build of the library is absent (__graft_entry__.build() makes it)")
-    script = (
-        "import sys, hashlib; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-        "import harness_lib, harness_adapters as wl, plonky3_recursion_amd as p3r\n"
-        "a = harness_lib.generate('koala-bear', 17, seed=5, horner_chain_len=64, sponge_chain_len=8, merkle_depth=20)\n"
-        "for zk in (0, 1):\n"
-        "    ctx = p3r.Context(field='koala-bear', zk=zk, zk_seed=3, allow_unpinned_w32_defaults=True)\n"
-        "    pc = p3r.PreparedCircuit(ctx, wl.circuit_from_arrays(a), p3r.TablePacking().with_fri_params(5, 2))\n"
-        "    print(hashlib.sha256(pc.prove(wl.circuit_inputs_from_arrays(a))).hexdigest())\n"
-        "    pc.free(); ctx.close()\n" % (ROOT, os.path.join(ROOT, "tests")))
-
-    def digests(**env):
-        r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600, env={**os.environ, **env})
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r.stdout.split()
-
-    want = digests()
-    assert len(want) == 2 and want[0] != want[1]
-    assert digests(P3R_LIB_PATH=knobs_lib) == want
-    assert digests(P3R_LIB_PATH=knobs_lib, P3R_COMMIT_OVERLAP="1") == want
-    assert digests(P3R_LIB_PATH=knobs_lib, P3R_COMMIT_OVERLAP="1", P3R_COMMIT_OVERLAP_MODE="2") == want

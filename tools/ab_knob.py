@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same-box A/B of one tuning knob of the `knobs` build of the library (plonky3_recursion_amd/knobs/libp3r_hip.so) on the
 headline layer: alternates `rounds` x (knob unset, knob set), each a fresh process of bench.py's timed region only.
-usage (GPU box): python tools/ab_knob.py P3R_NO_COMMIT_OVERLAP[=value] [rounds=3] [extra bench flags ...]"""
+usage (GPU box): python tools/ab_knob.py P3R_NTT_LINE_LOG_TILE[=value] [rounds=3] [extra bench flags ...]"""
 import json
 import os
 import subprocess
