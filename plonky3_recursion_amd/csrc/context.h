@@ -517,12 +517,13 @@ struct p3r_tree {
   int log_max_h = 0;
   int cap_height = 0;
   size_t total_width = 0;
-  // layers[l]: digests of layer l (layer 0 = leaves), SoA [8][n_l], n_l = 2^(log_max_h - l)
+  // Built by mmcs_impl.hip.h.  layers[l]: digests of layer l (layer 0 = leaves), SoA [8][layer_n[l]]; levels[l]
+  // (mmcs4.h) produces layers[l + 1] from layers[l], so an opening is levels[l].step - 1 siblings of layers[l] per level.
+  // Both arities are described this way (binary: every step 2, layer_n[l] = 2^(log_max_h - l); arity 4: a layer of 2 is
+  // padded to 4 with zero digests).  `arity` only says which permutation hashed the tree (2: width 16, 4: width 32).
   std::vector<p3r::DevBuf> layers;
-  // arity-4 MMCS (p3r_config.mmcs_arity = 4; mmcs4.h): levels[l] produces layers[l + 1]; n_l = layer_n[l] (a layer
-  // of 2 is padded to 4 with zero digests).  Empty for the binary tree.
   int arity = 2;
-  std::vector<p3r::Mmcs4Level> levels;
+  std::vector<p3r::MmcsLevel> levels;
   std::vector<size_t> layer_n;
 };
 

@@ -123,7 +123,7 @@ k_mmcs_hash_rows_strided_coop(const uint32_t* const* __restrict__ cols, int wtot
 }
 
 // Several levels of a Merkle tree per launch.  A workgroup owns `local` consecutive digests of the
-// input layer (32 by default, at most kSubtreeNodes; p3r_core.hip::subtree_nodes says why) and
+// input layer (32 by default, at most kSubtreeNodes; mmcs_impl.hip.h::subtree_nodes says why) and
 // everything above them: a barrier per level instead of a launch
 // (each of these levels is one permutation latency; the launches between them cost more than the
 // work), LDS hand-off between levels.  Every level is also written to its own layer buffer -

@@ -1,4 +1,4 @@
-// C ABI (include/p3r.h): context, device matrices, Poseidon2 (K3), coset LDE (K5), MMCS (K6).
+// C ABI (include/p3r.h): context, device matrices, Poseidon2 (K3), coset LDE (K5), MMCS (K6: mmcs_impl.hip.h).
 // Host orchestration only; all arithmetic on data runs in the gfx950 kernels of kernels.hip.h.
 #include "context.h"
 #include "kernels.hip.h"
@@ -180,303 +180,7 @@ std::unique_ptr<p3r_dmat> coset_lde(p3r_ctx* ctx, const p3r_dmat* in, int added_
   return std::move(coset_lde_batch<PP>(ctx, {{in, shift}}, added_bits)[0]);
 }
 
-// ------------------------------------------------------------------ MMCS
-// Row digests of several height classes in one launch: classes[c] = the matrices of one height
-// (their rows are concatenated in the given order), digs[c] = [8][h_c].
-template <class PP>
-void hash_rows(p3r_ctx* ctx, const std::vector<std::vector<const p3r_dmat*>>& classes,
-               const std::vector<uint32_t*>& digs) {
-  std::vector<HashRowsJob> jobs;
-  for (size_t c = 0; c < classes.size(); ++c) {
-    std::vector<const uint32_t*> cols;
-    for (const p3r_dmat* m : classes[c])
-      for (size_t k = 0; k < m->w; ++k) cols.push_back(m->d + k * m->h);
-    HashRowsJob j{};
-    j.cols = col_table(ctx, cols);
-    j.dig = digs[c];
-    j.h = classes[c][0]->h;
-    j.wtot = (int)cols.size();
-    jobs.push_back(j);
-  }
-  // widest rows first: their blocks run longest
-  std::stable_sort(jobs.begin(), jobs.end(),
-                   [](const HashRowsJob& a, const HashRowsJob& b) { return a.wtot > b.wtot; });
-  uint32_t blocks = 0;
-  double perms = 0;
-  for (auto& j : jobs) {
-    j.block0 = blocks;
-    blocks += blocks_for(j.h);
-    perms += (double)j.h * ((j.wtot + P2_RATE - 1) / P2_RATE);
-  }
-  prof_count(ctx, "hash_rows_perms", perms);
-  const auto* d_jobs =
-      static_cast<const HashRowsJob*>(const_table(ctx, jobs.data(), jobs.size() * sizeof(HashRowsJob)));
-  ProfScope ps(ctx, "mmcs_hash_rows");
-  hipLaunchKernelGGL(k_mmcs_hash_rows<PP>, dim3(blocks), dim3(kBlock), 0, ctx->stream, d_jobs, (int)jobs.size(),
-                     ctx->rcd());
-  P3R_HIP(hipGetLastError());
-}
-
-// One 2-to-1 layer, one permutation per lane: for layers large enough to fill the chip.  Smaller
-// ones are latency-bound and go through mmcs_subtree below (16 lanes per node, several levels per launch).
-// A lane-cooperative permutation costs 16 lanes x ~1.2 k instructions against ~3.9 k FP64 operations of one
-// lane: it is the faster way through a level only while the level is latency-bound, i.e. up to about
-// one 16-lane row per SIMD and pass (4096 nodes a pass on 256 CUs; a pass is ~2.7 us, a launch of the
-// one-permutation-per-lane kernel ~11 us whatever its size).  P3R_COOP_MAX_NODES / _LEAF_ROWS: tuning.
-// (tuning knobs are rounded down to a power of two: the kernels index by shifts and halvings)
-inline size_t env_pow2(const char* name, size_t dflt, size_t lo, size_t hi) {
-  const char* e = tuning_knob(name);
-  size_t v = e ? (size_t)atol(e) : dflt;
-  v = std::min(std::max(v, lo), hi);
-  while (v & (v - 1)) v &= v - 1;
-  return v;
-}
-inline size_t coop_max_nodes() {
-  static const size_t v = env_pow2("P3R_COOP_MAX_NODES", 16384, 1, size_t(1) << 30);
-  return v;
-}
-inline size_t coop_max_leaf_rows() {
-  static const size_t v = env_pow2("P3R_COOP_MAX_LEAF_ROWS", 8192, 1, size_t(1) << 30);
-  return v;
-}
-// Digests per workgroup of a k_mmcs_subtree launch: with 32, level 0 is one pass of 16 rows - one wave
-// per SIMD - and the five levels of the launch are all latency-bound; with 256 (eight levels per launch)
-// levels 0 and 1 queued 8 and 4 waves per SIMD on the few CUs that had a workgroup.
-inline size_t subtree_nodes() {
-  static const size_t v = env_pow2("P3R_SUBTREE_NODES", 32, 2, kSubtreeNodes);
-  return v;
-}
-template <class PP>
-void launch_compress(p3r_ctx* ctx, const uint32_t* prev, const uint32_t* inj, uint32_t* out, size_t n) {
-  ProfScope ps(ctx, "mmcs_compress");
-  hipLaunchKernelGGL(k_mmcs_compress<PP>, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, prev, inj, out, n,
-                     ctx->rcd());
-  P3R_HIP(hipGetLastError());
-}
-
-// log2(subtree_nodes()) levels above the `n`-digest layer at the back of `tree->layers` in one launch
-// (k_mmcs_subtree), for layers small enough to be latency-bound.  `inject`: height -> digests to
-// fold in at that height (may be null).  Returns the size of the new back layer, or `n` when
-// the layer is too large for this path.
-// `step`: FRI commit phase only - when this launch ends at the root (one workgroup, cap of one
-// digest) the transcript step runs inside it and `step->done` is set.
-struct TranscriptStep {
-  uint32_t *state, *beta, *cap;
-  bool done = false;
-  int dc = 4;   // words of the folding challenge (the challenge degree)
-};
-template <class PP>
-size_t mmcs_subtree(p3r_ctx* ctx, p3r_tree* tree, size_t n, const std::map<size_t, DevBuf>* inject,
-                    TranscriptStep* step = nullptr) {
-  const size_t cap_n = size_t(1) << tree->cap_height;
-  if (n / 2 > coop_max_nodes() || n <= cap_n) return n;
-  SubtreeArgs a{};
-  a.in = tree->layers.back().p;
-  a.n_in = (uint32_t)n;
-  const size_t local = std::min<size_t>(n, subtree_nodes());
-  a.local = (uint32_t)local;
-  size_t nn = n, shrink = local;
-  while (shrink > 1 && nn > cap_n && a.n_levels < kSubtreeLevels) {
-    nn /= 2;
-    shrink /= 2;
-    tree->layers.emplace_back(P2_DIGEST * nn);
-    a.out[a.n_levels] = tree->layers.back().p;
-    if (inject) {
-      auto it = inject->find(nn);
-      if (it != inject->end()) a.inj[a.n_levels] = it->second.p;
-    }
-    ++a.n_levels;
-  }
-  if (step && nn == 1 && n == local) {
-    a.t_state = step->state;
-    a.t_beta = step->beta;
-    a.t_cap = step->cap;
-    a.t_dc = step->dc;
-    step->done = true;
-  }
-  ProfScope ps(ctx, "mmcs_compress");
-  const unsigned lanes = (unsigned)std::min<size_t>(std::max<size_t>(local * 8, 64), kSubtreeBlock);
-  hipLaunchKernelGGL(k_mmcs_subtree<PP>, dim3((unsigned)(n / local)), dim3(lanes), 0, ctx->stream, a,
-                     ctx->rc.p, ctx->p2_diag.p);
-  P3R_HIP(hipGetLastError());
-  return nn;
-}
-
-// The levels of an arity-4 tree above its leaf-digest layer (tree->layers[0], tree->levels set): one launch each.
-// `inject`: height -> row digests of the matrices of that height (null: none, the FRI commit-phase trees).
-template <class PP>
-void mmcs4_build_levels(p3r_ctx* ctx, p3r_tree* tree, const std::map<size_t, DevBuf>* inject) {
-  for (const Mmcs4Level& lv : tree->levels) {
-    DevBuf next(P2_DIGEST * lv.padded_next);
-    const uint32_t* inj = nullptr;
-    if (lv.inject_h) {
-      auto it = inject ? inject->find(lv.inject_h) : decltype(inject->end()){};
-      if (!inject || it == inject->end() || lv.inject_h != lv.logical_next)
-        fail(P3R_EINVAL, "arity-4 MMCS: matrix heights must be powers of two");
-      inj = it->second.p;
-    }
-    mmcs4_compress<PP>(ctx, tree->layers.back().p, tree->layer_n.back(), lv.step, inj, next.p, lv.logical_next, lv.padded_next);
-    tree->layers.push_back(std::move(next));
-    tree->layer_n.push_back(lv.padded_next);
-  }
-}
-
-// The arity-4 tree (mmcs4.h; kernels_mmcs4.hip.h): leaf digests of every height class in one launch, then one launch
-// per level.  tree->layers[l] is [8][tree->layer_n[l]].
-template <class PP>
-void mmcs_commit4(p3r_ctx* ctx, p3r_tree* tree, uint32_t* cap_out) {
-  using F = Fp<PP>;
-  const auto& mats = tree->mats;
-  std::vector<size_t> heights, class_h;
-  for (auto* m : mats) heights.push_back(m->h);
-  std::vector<size_t> order(mats.size());
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return mats[a]->h > mats[b]->h; });
-  const size_t hmax = mats[order[0]]->h;
-  tree->arity = 4;
-  tree->log_max_h = log2_exact(hmax, "matrix height");
-  tree->cap_height = 0;
-  tree->total_width = 0;
-  for (auto* m : mats) tree->total_width += m->w;
-  tree->levels = mmcs4_schedule(heights);
-  for (size_t i : order)
-    if (class_h.empty() || class_h.back() != mats[i]->h) class_h.push_back(mats[i]->h);
-  tree->layers.clear();
-  tree->layer_n.clear();
-  const size_t n0 = mmcs4_padded_len(hmax);
-  tree->layers.emplace_back(P2_DIGEST * n0);
-  tree->layer_n.push_back(n0);
-  if (n0 != hmax) P3R_HIP(fill_async(ctx->stream, tree->layers[0].p, 0, P2_DIGEST * n0 * 4));
-  std::map<size_t, DevBuf> inject;
-  {
-    std::vector<std::vector<const p3r_dmat*>> classes;
-    std::vector<uint32_t*> digs;
-    std::vector<size_t> allocs;
-    for (size_t h : class_h) {
-      std::vector<const p3r_dmat*> v;
-      for (size_t i : order)
-        if (mats[i]->h == h) v.push_back(mats[i]);
-      classes.push_back(std::move(v));
-      if (h == hmax) { digs.push_back(tree->layers[0].p); allocs.push_back(n0); }
-      else { digs.push_back(inject.emplace(h, DevBuf(P2_DIGEST * h)).first->second.p); allocs.push_back(h); }
-    }
-    mmcs4_hash_rows<PP>(ctx, classes, digs, allocs);
-  }
-  mmcs4_build_levels<PP>(ctx, tree, &inject);
-  uint32_t root[P2_DIGEST];
-  P3R_HIP(fetch_small(ctx, tree->layers.back().p, P2_DIGEST, root));
-  for (int k = 0; k < P2_DIGEST; ++k) cap_out[k] = F::raw(root[k]).to_canonical();
-}
-
-template <class PP>
-void mmcs_commit(p3r_ctx* ctx, p3r_tree* tree, uint32_t* cap_out) {
-  using F = Fp<PP>;
-  const auto& mats = tree->mats;
-  if (mats.empty()) fail(P3R_EINVAL, "MMCS commit needs at least one matrix");
-  if (ctx->cfg.mmcs_arity == 4) return mmcs_commit4<PP>(ctx, tree, cap_out);
-  // tallest first, stable (recursion/src/pcs/mmcs.rs:355-425)
-  std::vector<size_t> order(mats.size());
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(),
-                   [&](size_t a, size_t b) { return mats[a]->h > mats[b]->h; });
-  const size_t hmax = mats[order[0]]->h;
-  tree->log_max_h = log2_exact(hmax, "matrix height");
-  tree->cap_height = (int)ctx->cfg.cap_height;
-  if (tree->cap_height > tree->log_max_h)
-    fail(P3R_EINVAL, "cap_height %d exceeds log2 of the tallest matrix (%d)", tree->cap_height,
-         tree->log_max_h);
-  tree->total_width = 0;
-  for (auto* m : mats) tree->total_width += m->w;
-
-  auto at_height = [&](size_t h) {
-    std::vector<const p3r_dmat*> v;
-    for (size_t i : order)
-      if (mats[i]->h == h) v.push_back(mats[i]);
-    return v;
-  };
-  // leaf digests of every height class up front, in one launch
-  std::vector<size_t> class_h;
-  for (size_t i : order)
-    if (class_h.empty() || class_h.back() != mats[i]->h) class_h.push_back(mats[i]->h);
-  tree->layers.clear();
-  std::map<size_t, DevBuf> inject;  // height -> digests of the matrices of that height
-  {
-    std::vector<std::vector<const p3r_dmat*>> classes;
-    std::vector<uint32_t*> digs;
-    for (size_t h : class_h) {
-      classes.push_back(at_height(h));
-      if (h == hmax) {
-        tree->layers.emplace_back(P2_DIGEST * hmax);
-        digs.push_back(tree->layers[0].p);
-      } else {
-        digs.push_back(inject.emplace(h, DevBuf(P2_DIGEST * h)).first->second.p);
-      }
-    }
-    hash_rows<PP>(ctx, classes, digs);
-  }
-  size_t n = hmax;
-  const size_t cap_n = size_t(1) << tree->cap_height;
-  while (n > cap_n) {
-    const size_t after = mmcs_subtree<PP>(ctx, tree, n, &inject);
-    if (after != n) {
-      n = after;
-      continue;
-    }
-    const size_t nn = n / 2;
-    DevBuf next(P2_DIGEST * nn);
-    const uint32_t* prev = tree->layers.back().p;
-    auto inj = inject.find(nn);
-    launch_compress<PP>(ctx, prev, inj != inject.end() ? inj->second.p : nullptr, next.p, nn);
-    tree->layers.push_back(std::move(next));
-    n = nn;
-  }
-  // cap: digest-major canonical
-  std::vector<uint32_t> soa(P2_DIGEST * cap_n);
-  P3R_HIP(fetch_small(ctx, tree->layers.back().p, soa.size(), soa.data()));
-  for (size_t j = 0; j < cap_n; ++j)
-    for (int k = 0; k < P2_DIGEST; ++k)
-      cap_out[j * P2_DIGEST + k] = F::raw(soa[(size_t)k * cap_n + j]).to_canonical();
-}
-
-template <class PP>
-void mmcs_open(p3r_ctx* ctx, const p3r_tree* tree, size_t index, uint32_t* opened, uint32_t* proof) {
-  using F = Fp<PP>;
-  if (index >> tree->log_max_h) fail(P3R_EINVAL, "open index %zu out of range", index);
-  size_t off = 0;
-  for (const p3r_dmat* m : tree->mats) {
-    int lh = log2_exact(m->h, "matrix height");
-    size_t row = index >> (tree->log_max_h - lh);
-    // strided gather of one row: w scattered 4-byte cells
-    P3R_HIP(hipMemcpy2DAsync(opened + off, 4, m->d + row, m->h * 4, 4, m->w, hipMemcpyDeviceToHost,
-                             ctx->stream));
-    off += m->w;
-  }
-  size_t depth = (size_t)(tree->log_max_h - tree->cap_height);
-  if (tree->arity == 4) {
-    // step - 1 siblings per level, ascending position, the node's own left out (recursion/src/pcs/mmcs.rs:1413-1461)
-    depth = 0;
-    for (size_t l = 0; l < tree->levels.size(); ++l) {
-      const size_t step = tree->levels[l].step, idx = index >> tree->levels[l].bits, pos = idx & (step - 1);
-      for (size_t j = 0; j < step; ++j) {
-        if (j == pos) continue;
-        P3R_HIP(hipMemcpy2DAsync(proof + depth * P2_DIGEST, 4, tree->layers[l].p + (idx - pos + j), tree->layer_n[l] * 4, 4,
-                                 P2_DIGEST, hipMemcpyDeviceToHost, ctx->stream));
-        ++depth;
-      }
-    }
-  } else {
-    for (size_t l = 0; l < depth; ++l) {
-      size_t n = size_t(1) << (tree->log_max_h - l);
-      size_t sib = (index >> l) ^ 1;
-      P3R_HIP(hipMemcpy2DAsync(proof + l * P2_DIGEST, 4, tree->layers[l].p + sib, n * 4, 4,
-                               P2_DIGEST, hipMemcpyDeviceToHost, ctx->stream));
-    }
-  }
-  P3R_HIP(hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < off; ++i) opened[i] = F::raw(opened[i]).to_canonical();
-  for (size_t i = 0; i < depth * P2_DIGEST; ++i) proof[i] = F::raw(proof[i]).to_canonical();
-}
-
+// ------------------------------------------------------------------ context
 template <class PP>
 void init_ctx(p3r_ctx* ctx) {
   using F = Fp<PP>;
@@ -547,9 +251,19 @@ void init_ctx(p3r_ctx* ctx) {
 
 }  // namespace
 
+#include "mmcs_impl.hip.h"
 #include "prove_impl.hip.h"
 #include "layer_impl.hip.h"
 #include "circuit_impl.hip.h"
+
+namespace {
+// MMCS commit as the ABI hands the cap out: canonical
+template <class PP>
+void mmcs_commit_canonical(p3r_ctx* ctx, p3r_tree* tree, uint32_t* cap_out) {
+  const std::vector<uint32_t> cap = mmcs_commit<PP>(ctx, tree);
+  for (size_t i = 0; i < cap.size(); ++i) cap_out[i] = Fp<PP>::raw(cap[i]).to_canonical();
+}
+}  // namespace
 
 // =============================================================================== C ABI
 extern "C" {
@@ -838,7 +552,7 @@ int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mat
     if (!mats || !cap_out || n_mats == 0) fail(P3R_EINVAL, "bad arguments");
     auto tree = std::make_unique<p3r_tree>();
     tree->mats.assign(mats, mats + n_mats);
-    P3R_FIELD_CALL(ctx, mmcs_commit, ctx, tree.get(), cap_out);
+    P3R_FIELD_CALL(ctx, mmcs_commit_canonical, ctx, tree.get(), cap_out);
     if (tree_out) *tree_out = tree.release();
   });
 }
@@ -854,7 +568,7 @@ int p3r_mmcs_commit(p3r_ctx* ctx, const p3r_matrix* mats, size_t n_mats, uint32_
           P3R_FIELD_CALL(ctx, upload, ctx, mats[i].values, mats[i].height, mats[i].width));
       tree->mats.push_back(tree->owned.back().get());
     }
-    P3R_FIELD_CALL(ctx, mmcs_commit, ctx, tree.get(), cap_out);
+    P3R_FIELD_CALL(ctx, mmcs_commit_canonical, ctx, tree.get(), cap_out);
     if (tree_out) *tree_out = tree.release();
   });
 }
@@ -868,9 +582,7 @@ int p3r_mmcs_open(p3r_ctx* ctx, const p3r_tree* tree, size_t index, uint32_t* op
 }
 size_t p3r_tree_log_max_height(const p3r_tree* t) { return (size_t)t->log_max_h; }
 size_t p3r_tree_total_width(const p3r_tree* t) { return t->total_width; }
-size_t p3r_tree_proof_len(const p3r_tree* t) {
-  return t->arity == 4 ? p3r::mmcs4_proof_len(t->levels) : (size_t)(t->log_max_h - t->cap_height);
-}
+size_t p3r_tree_proof_len(const p3r_tree* t) { return p3r::mmcs_proof_len(t->levels); }
 void p3r_tree_free(p3r_ctx* ctx, p3r_tree* tree) {
   if (ctx) (void)hipStreamSynchronize(ctx->stream);
   delete tree;

@@ -47,36 +47,6 @@ std::vector<typename Chal<PP, DC>::type> download_ef(p3r_ctx* ctx, const uint32_
   return out;
 }
 
-// Merkle layers above a leaf-digest layer (no injections): used by the FRI commit phase.
-template <class PP>
-void build_plain_layers(p3r_ctx* ctx, p3r_tree* tree, size_t n_leaves, TranscriptStep* step = nullptr) {
-  size_t n = n_leaves;
-  const size_t cap_n = size_t(1) << tree->cap_height;
-  while (n > cap_n) {
-    const size_t after = mmcs_subtree<PP>(ctx, tree, n, nullptr, step);
-    if (after != n) {
-      n = after;
-      continue;
-    }
-    const size_t nn = n / 2;
-    DevBuf next(P2_DIGEST * nn);
-    const uint32_t* prev = tree->layers.back().p;
-    launch_compress<PP>(ctx, prev, nullptr, next.p, nn);
-    tree->layers.push_back(std::move(next));
-    n = nn;
-  }
-}
-
-template <class PP>
-std::vector<uint32_t> download_cap_mont(p3r_ctx* ctx, const p3r_tree* tree) {
-  const size_t cap_n = size_t(1) << tree->cap_height;
-  std::vector<uint32_t> soa(P2_DIGEST * cap_n), cap(P2_DIGEST * cap_n);
-  P3R_HIP(fetch_small(ctx, tree->layers.back().p, soa.size(), soa.data()));
-  for (size_t j = 0; j < cap_n; ++j)
-    for (int k = 0; k < P2_DIGEST; ++k) cap[j * P2_DIGEST + k] = soa[(size_t)k * cap_n + j];
-  return cap;
-}
-
 // The context's generator key with a proof's nonce (zk_rand.h).
 inline ZkKey zk_key_of(const p3r_ctx* ctx, uint64_t nonce) {
   ZkKey k{};
@@ -135,10 +105,7 @@ std::unique_ptr<p3r_tree> commit_dmats(p3r_ctx* ctx, const std::vector<const p3r
     tree->mats.clear();
     for (size_t i = 0; i < mats.size(); ++i) { tree->mats.push_back(mats[i]); tree->mats.push_back(tree->salt_owned[i].get()); }
   }
-  std::vector<uint32_t> cap_canon((size_t)P2_DIGEST << ctx->cfg.cap_height);
-  mmcs_commit<PP>(ctx, tree.get(), cap_canon.data());
-  cap_mont.resize(cap_canon.size());
-  for (size_t i = 0; i < cap_canon.size(); ++i) cap_mont[i] = Fp<PP>::from_canonical(cap_canon[i]).v;
+  cap_mont = mmcs_commit<PP>(ctx, tree.get());
   return tree;
 }
 
@@ -364,9 +331,9 @@ struct BatchProver {
   std::vector<F> commit_pow_witnesses;
   std::vector<E> final_poly;
   F query_pow_witness;
-  // an opening proof inside a query's block: binary tree - `depth` sibling digests in a row at proof_at; arity-4 tree
-  // (mmcs4.h) - per level the siblings at positions pos ^ 1 .. pos ^ (step - 1), written out in ascending position
-  struct QPath { uint32_t proof_at = 0; int depth = 0; std::vector<uint32_t> lv_at; const p3r_tree* t = nullptr; };
+  // an opening proof inside a query's block, from `at` on: per level of the tree (mmcs4.h) the siblings at positions
+  // pos ^ 1 .. pos ^ (step - 1), written out in ascending position
+  struct QPath { uint32_t at = 0; const p3r_tree* t = nullptr; };
   struct QRound { std::vector<std::pair<uint32_t, uint32_t>> rows; QPath path; uint32_t tree_shift; };
   struct QPhase { uint32_t sib_at[8]; QPath path; int shift; uint32_t salt_at = 0; };
   std::vector<size_t> indices;
@@ -904,14 +871,13 @@ struct BatchProver {
       if (pi >= kMaxPhases) fail(P3R_EUNSUPPORTED, "more than %zu FRI commit phases", kMaxPhases);
       TranscriptStep step{d_tstate.p, d_betas + DC * pi, d_caps + P2_DIGEST * pi};
       step.dc = DC;
-      if (cfg.mmcs_arity == 4) mmcs4_build_levels<PP>(ctx, ph.tree.get(), nullptr);
-      else build_plain_layers<PP>(ctx, ph.tree.get(), rows, device_transcript ? &step : nullptr);
+      mmcs_build_levels<PP>(ctx, ph.tree.get(), nullptr, device_transcript ? &step : nullptr);
       if (device_transcript) {
         if (!step.done)  // a tree whose root is not produced by a single-workgroup launch (one leaf)
           hipLaunchKernelGGL(k_fri_transcript_step<PP>, dim3(1), dim3(64), 0, ctx->stream, ph.tree->layers.back().p,
                              step.state, step.beta, step.cap, ctx->rc.p, ctx->p2_diag.p, DC);
       } else {
-        ph.cap = download_cap_mont<PP>(ctx, ph.tree.get());
+        ph.cap = mmcs_cap_mont(ctx, ph.tree.get());
         for (uint32_t v : ph.cap) ch.observe(F::raw(v));
         commit_pow_witnesses.push_back(grind_witness<PP>(ctx, ch, (int)cfg.commit_pow_bits));
         const E beta = ch.sample_ext();
@@ -955,16 +921,12 @@ struct BatchProver {
   // The leaf digests of the commit phase that folds `folded` (2^log_cur rows) by 2^ph.la.
   void commit_phase_leaves(Phase& ph, int log_cur) {
     const size_t arity = size_t(1) << ph.la, rows = ph.rows, n_in = size_t(1) << log_cur;
-    // leaves: row r = the 2^la sibling evaluations, EF flattened -> column (j*DC+k) = plane k, offset j, stride arity
+    if ((int)cfg.cap_height > log_cur - ph.la)
+      fail(P3R_EINVAL, "cap_height %d exceeds the height of FRI commit phase %zu (2^%d rows)", (int)cfg.cap_height,
+           phases.size(), log_cur - ph.la);
     ph.tree = std::make_unique<p3r_tree>();
-    ph.tree->cap_height = (int)cfg.cap_height;
-    ph.tree->log_max_h = log_cur - ph.la;
-    if (ph.tree->cap_height > ph.tree->log_max_h)
-      fail(P3R_EINVAL, "cap_height %d exceeds the height of FRI commit phase %zu (2^%d rows)", ph.tree->cap_height,
-           phases.size(), ph.tree->log_max_h);
-    const bool arity4 = cfg.mmcs_arity == 4;
-    const size_t n_leaf = arity4 ? mmcs4_padded_len(rows) : rows;
-    ph.tree->layers.emplace_back(P2_DIGEST * n_leaf);
+    mmcs_begin(ctx, ph.tree.get(), {rows});
+    // leaves: row r = the 2^la sibling evaluations, EF flattened -> column (j*DC+k) = plane k, offset j, stride arity
     std::vector<const uint32_t*> cols;
     for (size_t j = 0; j < arity; ++j)
       for (int k = 0; k < DC; ++k) cols.push_back(folded.p + (size_t)k * n_in + j);
@@ -981,25 +943,7 @@ struct BatchProver {
       launch_zk_tiles<PP>(ctx, tj, zk_key, "mmcs_salts");
       for (uint32_t c = 0; c < S; ++c) cols.push_back(T.phase_salts.p + (size_t)c * n_in);
     }
-    const uint32_t* const* dcols = col_table(ctx, cols);
-    if (arity4) {
-      // ExtensionMmcs over the arity-4 MMCS: the same flattened rows under the width-32 sponge
-      ph.tree->arity = 4;
-      ph.tree->levels = mmcs4_schedule({rows});
-      ph.tree->layer_n.assign(1, n_leaf);
-      if (n_leaf != rows) P3R_HIP(fill_async(ctx->stream, ph.tree->layers[0].p, 0, P2_DIGEST * n_leaf * 4));
-      mmcs4_hash_rows_strided<PP>(ctx, dcols, (int)cols.size(), rows, arity, ph.tree->layers[0].p, n_leaf);
-    } else {
-      ProfScope ps(ctx, "mmcs_hash_rows_strided");
-      if (rows <= coop_max_leaf_rows())  // latency-bound: sixteen lanes per row
-        hipLaunchKernelGGL(k_mmcs_hash_rows_strided_coop<PP>, dim3(blocks_for(rows * 16)), dim3(kBlock), 0,
-                           ctx->stream, dcols, (int)cols.size(), rows, arity, ph.tree->layers[0].p, ctx->rc.p,
-                           ctx->p2_diag.p);
-      else
-        hipLaunchKernelGGL(k_mmcs_hash_rows_strided<PP>, dim3(blocks_for(rows)), dim3(kBlock), 0, ctx->stream,
-                           dcols, (int)cols.size(), rows, arity, ph.tree->layers[0].p, ctx->rcd());
-    }
-    P3R_HIP(hipGetLastError());
+    mmcs_hash_rows_strided<PP>(ctx, ph.tree.get(), cols, rows, arity);
   }
 
   // The final polynomial (host: <= 2^(log_final) extension elements); a device transcript is replayed on the host first
@@ -1065,21 +1009,10 @@ struct BatchProver {
     };
     // `base_shift`: the tree's index = query index >> base_shift
     auto push_path = [&](const p3r_tree* t, uint32_t base_shift) {
-      QPath qp;
-      qp.t = t;
-      qp.proof_at = cursor;
-      if (t->arity == 4) {
-        for (size_t l = 0; l < t->levels.size(); ++l) {
-          qp.lv_at.push_back(cursor);
-          for (int f = 1; f < t->levels[l].step; ++f)
-            push(t->layers[l].p, t->layer_n[l], P2_DIGEST, base_shift + (uint32_t)t->levels[l].bits, (uint32_t)f, 1);
-        }
-        qp.depth = (int)mmcs4_proof_len(t->levels);
-      } else {
-        qp.depth = t->log_max_h - t->cap_height;
-        for (int l = 0; l < qp.depth; ++l)
-          push(t->layers[l].p, size_t(1) << (t->log_max_h - l), P2_DIGEST, base_shift + l, 1, 1);
-      }
+      const QPath qp{cursor, t};
+      for (size_t l = 0; l < t->levels.size(); ++l)
+        for (int f = 1; f < t->levels[l].step; ++f)
+          push(t->layers[l].p, t->layer_n[l], P2_DIGEST, base_shift + (uint32_t)t->levels[l].bits, (uint32_t)f, 1);
       return qp;
     };
     for (Round* r : rounds()) {
@@ -1124,15 +1057,21 @@ struct BatchProver {
   }
 
   void write_path(const QPath& qp, const uint32_t* g, size_t tree_index) {
-    W.varint(qp.depth);
-    if (qp.t->arity != 4) {
-      W.words(g + qp.proof_at, (size_t)qp.depth * P2_DIGEST);
-      return;
-    }
-    for (size_t l = 0; l < qp.t->levels.size(); ++l) {
-      const size_t step = qp.t->levels[l].step, pos = (tree_index >> qp.t->levels[l].bits) & (step - 1);
+    W.varint(mmcs_proof_len(qp.t->levels));
+    const uint32_t* sibs = g + qp.at;   // of this level: the gathered positions pos ^ 1 .. pos ^ (step - 1)
+    const std::vector<MmcsLevel>& lv = qp.t->levels;
+    for (size_t l = 0; l < lv.size();) {
+      size_t run = 0;   // levels of step 2 have one sibling each, gathered in order: a run of them is written at once
+      while (l + run < lv.size() && lv[l + run].step == 2) ++run;
+      W.words(sibs, run * P2_DIGEST);
+      sibs += run * P2_DIGEST;
+      l += run;
+      if (l == lv.size()) break;
+      const size_t step = lv[l].step, pos = (tree_index >> lv[l].bits) & (step - 1);
       for (size_t j = 0; j < step; ++j)
-        if (j != pos) W.words(g + qp.lv_at[l] + ((j ^ pos) - 1) * P2_DIGEST, P2_DIGEST);
+        if (j != pos) W.words(sibs + ((j ^ pos) - 1) * P2_DIGEST, P2_DIGEST);
+      sibs += (step - 1) * P2_DIGEST;
+      ++l;
     }
   }
 

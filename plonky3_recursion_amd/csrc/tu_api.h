@@ -1,5 +1,6 @@
 // Functions that cross the translation units of libp3r_hip.so.  The library is several units so that they build
-// side by side (one unit took ten minutes): p3r_core.hip (C ABI, MMCS, prover sequencing, circuit boundary),
+// side by side (one unit took ten minutes): p3r_core.hip (C ABI, the Merkle tree module mmcs_impl.hip.h, prover
+// sequencing, circuit boundary),
 // tu_lde.hip (K5: NTT tables, passes and the coset LDE), tu_quotient.hip / tu_logup.hip (the two kernels with the
 // AIR constraint systems inlined, one instance per circuit degree and challenge degree), prep_device.hip.
 // Kernels never call across units; only these host entry points do.
@@ -55,7 +56,8 @@ void launch_logup_aux(p3r_ctx* ctx, unsigned blocks, const LogupJob* d_jobs, int
 template <class PP, int DC>
 void launch_quotient(p3r_ctx* ctx, unsigned blocks, const QuotientArgs* d_jobs, int n_jobs, const LookupChT<DC>& lc);
 
-// K6 of the arity-4 MMCS (tu_mmcs4.hip; kernels_mmcs4.hip.h).  classes[c] = the matrices of one height, digs[c] =
+// K6 of the arity-4 MMCS (tu_mmcs4.hip; kernels_mmcs4.hip.h), launched by the tree module (mmcs_impl.hip.h).
+// classes[c] = the matrices of one height, digs[c] =
 // [8][allocs[c]] with allocs[c] >= that height.
 template <class PP>
 void mmcs4_hash_rows(p3r_ctx* ctx, const std::vector<std::vector<const p3r_dmat*>>& classes, const std::vector<uint32_t*>& digs,

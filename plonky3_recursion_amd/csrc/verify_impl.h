@@ -683,9 +683,9 @@ void mmcs_verify4(const std::vector<std::array<Fp<PP>, P2_DIGEST>>& cap, int cap
     heights.push_back(size_t(1) << lh);
   }
   if (index >> log_max) vfail("%s: index out of range", what);
-  const std::vector<Mmcs4Level> levels = mmcs4_schedule(heights);
-  if (path.size() != mmcs4_proof_len(levels))
-    vfail("%s: opening proof has %zu siblings, expected %zu", what, path.size(), mmcs4_proof_len(levels));
+  const std::vector<MmcsLevel> levels = mmcs4_schedule(heights);
+  if (path.size() != mmcs_proof_len(levels))
+    vfail("%s: opening proof has %zu siblings, expected %zu", what, path.size(), mmcs_proof_len(levels));
   auto concat = [&](size_t h) {
     std::vector<F> r;
     for (size_t m = 0; m < rows.size(); ++m)
@@ -696,7 +696,7 @@ void mmcs_verify4(const std::vector<std::array<Fp<PP>, P2_DIGEST>>& cap, int cap
   zero.fill(F::zero());
   Digest node = sponge_hash_w32<PP>(concat(size_t(1) << log_max), rcw);
   size_t at = 0;
-  for (const Mmcs4Level& lv : levels) {
+  for (const MmcsLevel& lv : levels) {
     const size_t pos = (index >> lv.bits) & (size_t)(lv.step - 1);
     Digest c[4] = {zero, zero, zero, zero};
     for (size_t j = 0; j < (size_t)lv.step; ++j) c[j] = j == pos ? node : path[at++];
