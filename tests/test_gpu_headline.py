@@ -3,7 +3,14 @@ and BabyBear 2^22 rows (config 5) - with the default FRI parameters.  They take 
 smaller tests do not (balanced four-step NTT splits, 4 M / 16 M-leaf trees, > 2^31-cell matrices,
 multi-GB pools): the proof of prove_next_layer is checked by BOTH verifiers (native
 `verify_all_tables`, and the oracle's restatement of the in-tree circuit verifier), tampering is
-rejected, and the LDE + MMCS commit of a tall narrow matrix is compared bit for bit with the oracle."""
+rejected, and the LDE + MMCS commit of a tall narrow matrix is compared bit for bit with the oracle.  Where
+tests/golden/proof_digests_large.json pins the size (tools/gen_proof_digests.py --large), the preprocessed commitment
+and the proof bytes must be the CPU oracle's as well."""
+import hashlib
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -16,6 +23,14 @@ pytestmark = pytest.mark.gpu
 FRI = dict(log_blowup=2, max_log_arity=2, cap_height=0, log_final_poly_len=5, commit_pow_bits=0,
            query_pow_bits=15, num_queries=54)  # the reference examples' defaults (= bench.py)
 GEN = dict(horner_chain_len=64, sponge_chain_len=8, merkle_depth=20)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+spec = importlib.util.spec_from_file_location("gen_proof_digests", os.path.join(ROOT, "tools", "gen_proof_digests.py"))
+gpd = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(gpd)
+PINS = json.load(open(gpd.LARGE_PATH))["cases"]
+# the oracle's digests of these very layers; BabyBear 2^22 is not pinned (the fixture's provenance says why)
+PINNED = {("koala-bear", 20): "kb_headline_20"}
 
 
 @pytest.mark.parametrize("field,log_h", [("koala-bear", 20), ("baby-bear", 22)])
@@ -35,11 +50,18 @@ def test_headline_layer_proves_and_both_verifiers_accept(oracle, field, log_h):
                                p3r.ProveNextLayerParams(table_packing=tp), prep=cache)
     cpd = cache.circuit_prover_data
     assert max(cpd.table_heights) == 1 << log_h
+    if (field, log_h) in PINNED:
+        # byte parity with the CPU oracle's prover at the size of the metric
+        case = gpd.LARGE_BY_NAME[PINNED[(field, log_h)]]
+        pin = PINS[case["name"]]
+        assert (case["field"], case["log_h"], case["seed"], case["gen"], dict(gpd.FRI, **case["prm"])) == (field, log_h, 0x5EED0000, GEN, FRI)
+        assert hashlib.sha256(np.ascontiguousarray(cpd.preprocessed_commitment, dtype=np.uint32).tobytes()).hexdigest() == pin["prep_commit"]
+        if len(out.proof.proof) != pin["proof_bytes"] or hashlib.sha256(out.proof.proof).hexdigest() != pin["proof"]:
+            pytest.fail(gpd.describe_mismatch(pin, out.proof.proof, case), pytrace=False)
     # a second prove of the same inputs gives the same bytes (no stale pooled memory at this size)
     assert cache.prepared_circuit.prove(inputs) == out.proof.proof
     # the host restatement of the preparation (csrc/circuit_impl.hip.h) agrees with the device pass at this size:
     # same preprocessed commitment, same schedule depth, same proof
-    import os
     os.environ["P3R_PREP_HOST"] = "1"
     try:
         host_pc = p3r.PreparedCircuit(ctx, circuit, tp)

@@ -1,6 +1,9 @@
-"""GPU: larger layers where the CPU oracle PROVER would take minutes - the GPU proof is checked by
-the oracle VERIFIER (restatement of the in-tree circuit verifier) instead, against the GPU's own
-preprocessed commitment (itself compared with the oracle's at small sizes in test_gpu_layer.py)."""
+"""GPU: larger layers, where the CPU oracle PROVER takes too long to run inside a test - the GPU proof is
+checked by the oracle VERIFIER (restatement of the in-tree circuit verifier) here, against the GPU's own
+preprocessed commitment (itself compared with the oracle's at small sizes in test_gpu_layer.py).
+Byte parity with the oracle's prover at these sizes is carried by its committed digests
+(tests/golden/proof_digests_large.json: tests/test_gpu_large_digests.py); these tests stay as the
+verifier-side check of the same sizes."""
 import numpy as np
 import pytest
 
