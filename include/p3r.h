@@ -71,7 +71,8 @@ typedef struct p3r_config {
                                 * circuits too: constants carry D coefficients, inputs are n x D, Poseidon2 ops are
                                 * base-mode permutations (p3r_op_kind). */
   uint32_t log_blowup;
-  uint32_t max_log_arity;
+  uint32_t max_log_arity;      /* 1..4 on the device prover: a commit phase folds by at most 16 (the reference's usual
+                                * setting is 4); a phase the rule or the schedule makes wider is P3R_EUNSUPPORTED */
   uint32_t cap_height;
   uint32_t log_final_poly_len;
   uint32_t commit_pow_bits;

@@ -574,58 +574,90 @@ k_open_reduce(const OpenJob* __restrict__ jobs, int n_jobs, uint32_t total, uint
 }
 
 // ------------------------------------------------------------------ K10: FRI
-// One commit-phase fold of arity 2^la: la sequential arity-2 folds with beta, beta^2, ...
-// (recursion/src/pcs/fri/verifier.rs:562-781), then the roll-in  + beta^{2^la} * ro.
+// One commit-phase fold of arity 2^LA (LA = 1..4): LA sequential arity-2 folds with beta, beta^2, ...
+// (recursion/src/pcs/fri/verifier.rs:562-781), then the roll-in  + beta^{2^LA} * ro.
 struct FriFoldArgs {
-  const uint32_t* in;   // [4][rows << la]
-  uint32_t* out;        // [4][rows]
+  const uint32_t* in;   // [DC][rows << LA]
+  uint32_t* out;        // [DC][rows]
   size_t rows;
-  int la, log_rows;
-  const uint32_t* beta; // the phase's folding challenge, 4 words on the device (written by the
+  int log_rows;
+  const uint32_t* beta; // the phase's folding challenge, DC words on the device (written by the
                         // device-side transcript step, or uploaded by the host)
-  const uint32_t* roll; // nullable [4][rows]
-  uint32_t w_inv;       // inverse generator of the domain of size rows << la
-  uint32_t tw_inv[3][4];  // tw_inv[s][j] = (w_arity^{2^s})^{-bitrev(2j, la - s)}
+  const uint32_t* roll; // nullable [DC][rows]
+  uint32_t w_inv;       // inverse generator of the domain of size rows << LA
+  uint32_t tw_inv[4][8];  // tw_inv[s][j] = (w_arity^{2^s})^{-bitrev(2j, LA - s)}
   uint32_t neg_half;
 };
-template <class PP, int DC = 4>
-__global__ void __launch_bounds__(kBlock) k_fri_fold(FriFoldArgs a) {
+typedef uint32_t fri_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t fri_u32x4 __attribute__((ext_vector_type(4)));
+// Arity-2 fold number S of the LA: e[0 .. 2^(LA-S)) -> e[0 .. 2^(LA-S-1)), in ascending order, then the next one.  (A
+// recursion over S rather than a loop: every index into `e` and `tw_inv` is a constant whatever the unroller decides.)
+template <class PP, int DC, int LA, int S>
+__device__ __forceinline__ void fri_fold_steps(typename Chal<PP, DC>::type* e, typename Chal<PP, DC>::type& b, Fp<PP>& ss_inv,
+                                               const Fp<PP> nh, const uint32_t (&tw_inv)[4][8]) {
   using F = Fp<PP>;
   using E = typename Chal<PP, DC>::type;
-  size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
-  if (r >= a.rows) return;
-  const size_t n_in = a.rows << a.la;
-  E e[8];
-  const int arity = 1 << a.la;
-  for (int j = 0; j < arity; ++j)
+  if constexpr (S < LA) {
 #pragma unroll
-    for (int k = 0; k < DC; ++k) e[j].c[k] = F::raw(a.in[(size_t)k * n_in + (r << a.la) + j]);
-  F ss_inv = F::raw(a.w_inv).pow(bit_reverse((uint32_t)r, a.log_rows));
-  E b;
-#pragma unroll
-  for (int k = 0; k < DC; ++k) b.c[k] = F::raw(a.beta[k]);
-  const F nh = F::raw(a.neg_half);
-  int len = arity;
-  for (int s = 0; s < a.la; ++s) {
-    for (int j = 0; j < len / 2; ++j) {
-      F x0_inv = ss_inv * F::raw(a.tw_inv[s][j]);
+    for (int j = 0; j < (1 << (LA - S - 1)); ++j) {
+      F x0_inv = ss_inv * F::raw(tw_inv[S][j]);
       // e0 + (beta - x0)(e1 - e0)(-1/2)/x0  =  e0 + (beta/x0 - 1)(e1 - e0)(-1/2)
       E t = b * x0_inv - E::one();
       e[j] = e[2 * j] + t * (e[2 * j + 1] - e[2 * j]) * nh;
     }
-    len /= 2;
     ss_inv = ss_inv.sqr();
     b = b.sqr();
+    fri_fold_steps<PP, DC, LA, S + 1>(e, b, ss_inv, nh, tw_inv);
   }
+}
+// One instance per (field, DC, LA): the sibling array, the loops and the twiddle indices are compile-time shapes, so the
+// 2^LA extension elements of a row stay in registers (80 words at LA = 4, DC = 5; register and scratch figures of every
+// instance: profiles/r07/fri_arity.txt).  A lane's
+// siblings in one plane are adjacent - 4 << LA bytes at a multiple of that from the plane's start, every plane 16-byte
+// aligned (the buffers are device allocations and a plane is rows << LA words) - and are read with 16-byte loads (8-byte
+// at LA = 1): a wave asks for one contiguous span per plane (4 KB at LA = 4) instead of 2^LA strided dwords.
+template <class PP, int DC, int LA>
+__global__ void __launch_bounds__(kBlock) k_fri_fold(FriFoldArgs a) {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  static_assert(LA >= 1 && LA <= 4, "folds by 2, 4, 8 or 16");
+  constexpr int ARITY = 1 << LA;
+  size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= a.rows) return;
+  const size_t n_in = a.rows << LA;
+  E e[ARITY];
+#pragma unroll
+  for (int k = 0; k < DC; ++k) {
+    const gptr<const uint32_t> row = as_global(a.in) + (size_t)k * n_in + (r << LA);
+    if constexpr (LA == 1) {
+      const fri_u32x2 v = *(gptr<const fri_u32x2>)row;
+      e[0].c[k] = F::raw(v.x);
+      e[1].c[k] = F::raw(v.y);
+    } else {
+#pragma unroll
+      for (int q = 0; q < ARITY / 4; ++q) {
+        const fri_u32x4 v = ((gptr<const fri_u32x4>)row)[q];
+        e[4 * q].c[k] = F::raw(v.x);
+        e[4 * q + 1].c[k] = F::raw(v.y);
+        e[4 * q + 2].c[k] = F::raw(v.z);
+        e[4 * q + 3].c[k] = F::raw(v.w);
+      }
+    }
+  }
+  F ss_inv = F::raw(a.w_inv).pow(bit_reverse((uint32_t)r, a.log_rows));
+  E b;
+#pragma unroll
+  for (int k = 0; k < DC; ++k) b.c[k] = F::raw(as_global(a.beta)[k]);
+  fri_fold_steps<PP, DC, LA, 0>(e, b, ss_inv, F::raw(a.neg_half), a.tw_inv);
   E res = e[0];
   if (a.roll) {
     E ro;
 #pragma unroll
-    for (int k = 0; k < DC; ++k) ro.c[k] = F::raw(a.roll[(size_t)k * a.rows + r]);
-    res += b * ro;  // b is beta^(2^la) after the la squarings above
+    for (int k = 0; k < DC; ++k) ro.c[k] = F::raw(as_global(a.roll)[(size_t)k * a.rows + r]);
+    res += b * ro;  // b is beta^(2^LA) after the LA squarings above
   }
 #pragma unroll
-  for (int k = 0; k < DC; ++k) a.out[(size_t)k * a.rows + r] = res.c[k].v;
+  for (int k = 0; k < DC; ++k) as_global(a.out)[(size_t)k * a.rows + r] = res.c[k].v;
 }
 
 // Leaf hashing for column sets that are strided views (FRI commit-phase leaves are the

@@ -335,7 +335,7 @@ struct BatchProver {
   // pos ^ 1 .. pos ^ (step - 1), written out in ascending position
   struct QPath { uint32_t at = 0; const p3r_tree* t = nullptr; };
   struct QRound { std::vector<std::pair<uint32_t, uint32_t>> rows; QPath path; uint32_t tree_shift; };
-  struct QPhase { uint32_t sib_at[8]; QPath path; int shift; uint32_t salt_at = 0; };
+  struct QPhase { uint32_t sib_at[16]; QPath path; int shift; uint32_t salt_at = 0; };
   std::vector<size_t> indices;
   std::vector<QRound> qrounds;
   std::vector<QPhase> qphases;
@@ -863,7 +863,7 @@ struct BatchProver {
       int log_next = next_h < heights.size() ? heights[next_h] : -1;
       int la = fri_log_arity(ctx->fri_log_arities, phases.size(), (int)cfg.max_log_arity, log_cur, log_final, log_next);
       if (la < 0) fail(P3R_EINVAL, "fri_log_arities does not fit the proof: phase %zu at height 2^%d", phases.size(), log_cur);
-      if (la > 3) fail(P3R_EUNSUPPORTED, "max_log_arity > 3 is not supported");
+      if (la > 4) fail(P3R_EUNSUPPORTED, "max_log_arity > 4 is not supported");
       const size_t arity = size_t(1) << la, rows = (size_t(1) << log_cur) >> la;
       Phase ph{la, rows};
       commit_phase_leaves(ph, log_cur);
@@ -887,7 +887,7 @@ struct BatchProver {
       }
       DevBuf out(DC * rows);
       FriFoldArgs fa{};
-      fa.in = folded.p; fa.out = out.p; fa.rows = rows; fa.la = la; fa.log_rows = log_cur - la;
+      fa.in = folded.p; fa.out = out.p; fa.rows = rows; fa.log_rows = log_cur - la;
       fa.beta = d_betas + DC * pi;
       const bool roll = next_h < heights.size() && heights[next_h] == log_cur - la;
       fa.roll = roll ? ros[heights[next_h]].second.p : nullptr;
@@ -901,7 +901,10 @@ struct BatchProver {
       fa.neg_half = (-(F::from_canonical(2).inv())).v;
       {
         ProfScope ps(ctx, "fri_fold");
-        hipLaunchKernelGGL((k_fri_fold<PP, DC>), dim3(blocks_for(rows)), dim3(kBlock), 0, ctx->stream, fa);
+        // one instance per arity (kernels_stark.hip.h)
+        static constexpr void (*kFold[4])(FriFoldArgs) = {k_fri_fold<PP, DC, 1>, k_fri_fold<PP, DC, 2>, k_fri_fold<PP, DC, 3>,
+                                                          k_fri_fold<PP, DC, 4>};
+        hipLaunchKernelGGL(kFold[la - 1], dim3(blocks_for(rows)), dim3(kBlock), 0, ctx->stream, fa);
       }
       P3R_HIP(hipGetLastError());
       if (roll) ++next_h;

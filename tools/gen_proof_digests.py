@@ -1,7 +1,9 @@
 """Digests of the oracle's proof bytes for a fixed list of small layers -> tests/golden/proof_digests.json.
    python3 tools/gen_proof_digests.py
    python3 tools/gen_proof_digests.py --large [--only NAME[,NAME]]    -> tests/golden/proof_digests_large.json
+   python3 tools/gen_proof_digests.py --arity16 [--only NAME[,NAME]]  -> tests/golden/proof_digests_arity16.json
    python3 tools/gen_proof_digests.py --check NAME[,NAME] | all       regenerate and compare, write nothing
+   python3 tools/gen_proof_digests.py --arity16 --check all           the same for the arity-16 fixture
 Not a parity pin (the reference holds no proof bytes): a DRIFT pin.  The oracle, the generator and
 the device prover change together from round to round; these digests make a change of the proof bytes of an existing
 configuration visible in review instead of silently re-agreeing with itself.  `workload` is the digest of the
@@ -11,7 +13,9 @@ generator's arrays, so a generator change is told apart from a prover change.
 examples' FRI defaults.  CPU only (the oracle under OpenMP; minutes per case at 2^20).  The oracle's grinding takes the
 smallest witness and its FRI schedule is the reference's rule, so at these sizes the digests are a PARITY pin for the
 device prover: the branches it only takes there (balanced NTT splits, multi-launch Merkle levels, multi-tile scans and
-sorts) must give the oracle's bytes, not merely bytes a verifier accepts.  Next to the whole-proof digest every entry
+sorts) must give the oracle's bytes, not merely bytes a verifier accepts.  --arity16: ARITY16_CASES, the bench workload
+and the arity-4-MMCS recursion layer under max_log_arity = 4 (FRI folding by 16, the reference's documented default), in
+a fixture of their own with the same record shape.  Next to the whole-proof digest every entry
 holds one digest per decoded section of the proof (tests/proof_codec.py), in protocol order, so that a mismatch names
 the first phase that differs.  One child process per case, so that `peak_rss_gb` is the case's own."""
 import hashlib
@@ -106,6 +110,25 @@ LARGE_CASES = [
     _large("kb_zk_hiding_16", "koala-bear", 16, zk=1, num_random_codewords=2, zk_key=ZK_KEY, mmcs_salt_elems=4),
 ]
 LARGE_BY_NAME = {c["name"]: c for c in LARGE_CASES}
+
+# max_log_arity = 4: the bench workload at 2^14, 2^16 and 2^20 rows, and the arity-4-MMCS recursion layer at 2^16.  Each folds
+# by 16 once the last table height is rolled in (2^14 rows: log_arity 1, 1, 2, 4, 1 - heights 2^16, 2^15, 2^14, 2^12, then
+# 2^12 -> 2^8 -> the final 2^7); tests/test_fri_arity16.py asserts it on the decoded proof.
+ARITY16_PATH = os.path.join(ROOT, "tests", "golden", "proof_digests_arity16.json")
+ARITY16_CASES = [
+    _large("kb_headline_14_la4", "koala-bear", 14, max_log_arity=4),
+    _large("kb_headline_16_la4", "koala-bear", 16, max_log_arity=4),
+    _large("kb_headline_20_la4", "koala-bear", 20, max_log_arity=4),
+    _large("kb_arity4_w32_ops_16_la4", "koala-bear", 16, seed=0x5EED0032, flags=4096 | 128, mmcs_arity=4, max_log_arity=4),
+]
+ARITY16_BY_NAME = {c["name"]: c for c in ARITY16_CASES}
+
+
+def fri_log_arities(proof, case):
+    """The log2 arities of the commit phases, read off the first query of the proof."""
+    import proof_codec
+    p = proof_codec.decode(proof, **large_codec_kw(case))
+    return [s["log_arity"] for s in p["opening_proof"]["query_proofs"][0]["commit_phase_openings"]]
 
 
 def sha_json(x):
@@ -261,11 +284,12 @@ def _child_entry(name):
     return json.loads(out.stdout.decode().strip().splitlines()[-1])
 
 
-def _names(arg):
-    names = [c["name"] for c in LARGE_CASES] if arg in (None, "all") else [n for n in arg.split(",") if n]
+def _names(arg, cases=LARGE_CASES):
+    known = [c["name"] for c in cases]
+    names = known if arg in (None, "all") else [n for n in arg.split(",") if n]
     for n in names:
-        if n not in LARGE_BY_NAME:
-            raise SystemExit(f"unknown large case {n!r}; known: {', '.join(LARGE_BY_NAME)}")
+        if n not in known:
+            raise SystemExit(f"unknown case {n!r}; known: {', '.join(known)}")
     return names
 
 
@@ -274,11 +298,11 @@ def compare_entries(pin, got):
     return [k for k in sorted(set(pin) | set(got)) if k not in RECORDED and pin.get(k) != got.get(k)]
 
 
-def main_large(only=None, check=None):
-    fixture = json.load(open(LARGE_PATH)) if os.path.exists(LARGE_PATH) else {"provenance": {}, "cases": {}}
+def main_large(only=None, check=None, path=LARGE_PATH, cases=LARGE_CASES):
+    fixture = json.load(open(path)) if os.path.exists(path) else {"provenance": {}, "cases": {}}
     if check is not None:
         bad = 0
-        for n in _names(check):
+        for n in _names(check, cases):
             if n not in fixture["cases"]:
                 print(f"{n}: not in the fixture")
                 bad += 1
@@ -291,24 +315,24 @@ def main_large(only=None, check=None):
                   flush=True)
             bad += bool(diff)
         sys.exit(1 if bad else 0)
-    for n in _names(only):   # written after every case: a case is minutes of work
+    for n in _names(only, cases):   # written after every case: a case is minutes of work
         fixture["cases"][n] = _child_entry(n)
         print(f"{n}: {fixture['cases'][n]['proof_bytes']} bytes, {fixture['cases'][n]['oracle_seconds']} s", flush=True)
-        fixture = _write_large(fixture)
+        fixture = _write_large(fixture, path, cases)
 
 
-def _write_large(fixture):
+def _write_large(fixture, path=LARGE_PATH, cases=LARGE_CASES):
     prov = fixture["provenance"] if isinstance(fixture.get("provenance"), dict) else {}
-    prov["tool"] = ("tools/gen_proof_digests.py --large: sha256 of the CPU oracle's prove_batch bytes (Montgomery encoding), of the "
+    prov["tool"] = ("tools/gen_proof_digests.py " + ("--large" if path == LARGE_PATH else "--arity16") + ": sha256 of the CPU oracle's prove_batch bytes (Montgomery encoding), of the "
                     "preprocessed commitment and of every decoded section of the proof; digests only, no proof bytes. "
                     "oracle_seconds / threads / peak_rss_gb are recorded, not asserted")
     prov.setdefault("records", [])   # hand-kept: what was checked, and what was left out and why
-    order = [c["name"] for c in LARGE_CASES]
+    order = [c["name"] for c in cases]
     fixture = {"provenance": prov, "cases": {n: fixture["cases"][n] for n in order if n in fixture["cases"]}}
-    with open(LARGE_PATH, "w") as fh:
+    with open(path, "w") as fh:
         json.dump(fixture, fh, indent=1)
         fh.write("\n")
-    print("wrote", LARGE_PATH, flush=True)
+    print("wrote", path, flush=True)
     return fixture
 
 
@@ -336,13 +360,17 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--large", action="store_true", help="write tests/golden/proof_digests_large.json (CPU only)")
+    ap.add_argument("--arity16", action="store_true",
+                    help="write tests/golden/proof_digests_arity16.json: max_log_arity = 4 (CPU only); with --check, re-derive it")
     ap.add_argument("--only", metavar="NAME[,NAME]", help="--large: regenerate these cases only, keep the others")
     ap.add_argument("--check", metavar="NAME[,NAME]", help="regenerate these large cases (or `all`) and compare; writes nothing")
     ap.add_argument("--emit", metavar="NAME", help=argparse.SUPPRESS)   # the child of --large / --check: one entry on stdout
     args = ap.parse_args()
     if args.emit:
         import oracle_lib
-        print(json.dumps(large_entry(oracle_lib.Oracle(), LARGE_BY_NAME[args.emit])))
+        print(json.dumps(large_entry(oracle_lib.Oracle(), dict(LARGE_BY_NAME, **ARITY16_BY_NAME)[args.emit])))
+    elif args.arity16:
+        main_large(only=args.only, check=args.check, path=ARITY16_PATH, cases=ARITY16_CASES)
     elif args.large or args.check or args.only:
         main_large(only=args.only, check=args.check)
     else:

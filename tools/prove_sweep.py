@@ -3,7 +3,9 @@ cap heights, proof-of-work bits, folding schedules and the selectable protocol d
 combinations than tests/test_gpu_layer.py and tests/test_gpu_prove.py run.  For every draw the proof
 bytes of the HIP prover must equal the oracle's, and both verifiers must accept them.
 
-usage: python tools/prove_sweep.py [first_seed] [count] [max_log_h] [min_log_h]     (needs a GPU; oracle = checker)
+usage: python tools/prove_sweep.py [--max-log-arity-4] [first_seed] [count] [max_log_h] [min_log_h]     (needs a GPU; oracle = checker)
+--max-log-arity-4: every draw's max_log_arity is raised to 4 (FRI folding by 16) after the seeded draws are made, so the
+default sweep keeps its draws; the summary then also counts the draws whose proof really holds a 16-ary phase.
 """
 import random
 import sys
@@ -21,6 +23,7 @@ import plonky3_recursion_amd as p3r
 from plonky3_recursion_amd import prover as pv
 
 P3R_EXT_LOOKUP_UNPACKED = 1
+FOLDED_BY_16 = [0, 0]   # --max-log-arity-4: proofs that hold a 16-ary phase, draws refused by both sides
 
 
 def draw(rng, max_log_h, min_log_h=5):
@@ -74,9 +77,20 @@ def fitting_schedule(rng, oracle, field, arrs, kw, packing):
     return out
 
 
-def one(oracle, seed, max_log_h, min_log_h=5):
+def folds_by_16(proof, kw):
+    """Whether the first query of the proof opens a 16-ary commit phase."""
+    import proof_codec
+    if kw.get("proof_layout") is not None:
+        return None   # (the test codec reads the identity field order only)
+    d = proof_codec.decode(proof, dc=kw.get("challenge_degree", 4), zk=bool(kw.get("zk")), salted=bool(kw.get("mmcs_salt_elems")))
+    return any(s["log_arity"] == 4 for s in d["opening_proof"]["query_proofs"][0]["commit_phase_openings"])
+
+
+def one(oracle, seed, max_log_h, min_log_h=5, max_log_arity_4=False):
     rng = random.Random(seed)
     field, log_h, kw, packing, gen = draw(rng, max_log_h, min_log_h)
+    if max_log_arity_4:
+        kw["max_log_arity"] = 4   # (after the draws: the rule and the fitting schedules now reach 16-ary phases)
     # circuit extension degree and table variants, from a second stream so that the draws above keep their seeds:
     # D = 5 (KoalaBear quintic circuits: primitive tables, + compact-D1 Poseidon2, + Recompose, + recompose/coeff) in
     # a third of the KoalaBear draws; recompose/coeff under D = 4 now and then
@@ -171,12 +185,17 @@ def one(oracle, seed, max_log_h, min_log_h=5):
         assert want_cap is None, "prover refused (%s) what the oracle proves: %s" % (e, desc)
         if ctx is not None:
             ctx.close()
+        if max_log_arity_4:
+            FOLDED_BY_16[1] += 1
         return desc + "  [refused by both: " + want + "]", 0
     assert want_cap is not None, "prover accepted what the oracle refuses (%s): %s" % (want, desc)
     assert np.array_equal(cpd.preprocessed_commitment, want_cap), "prep commitment: " + desc
     assert out.proof == want, "proof bytes: " + desc
     L.verify(out.proof)
     cache.prover.verify_all_tables(out)
+    if max_log_arity_4 and folds_by_16(out.proof, kw):
+        FOLDED_BY_16[0] += 1
+        desc += "  [16-ary phase]"
     if cache.prepared_circuit is not None:
         cache.prepared_circuit.free()
     else:
@@ -186,16 +205,23 @@ def one(oracle, seed, max_log_h, min_log_h=5):
 
 
 def main():
-    first = int(sys.argv[1]) if len(sys.argv) > 1 else 5000
-    count = int(sys.argv[2]) if len(sys.argv) > 2 else 100
-    max_log_h = int(sys.argv[3]) if len(sys.argv) > 3 else 12
-    min_log_h = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+    argv = [a for a in sys.argv[1:] if a != "--max-log-arity-4"]
+    la4 = len(argv) != len(sys.argv) - 1
+    first = int(argv[0]) if len(argv) > 0 else 5000
+    count = int(argv[1]) if len(argv) > 1 else 100
+    max_log_h = int(argv[2]) if len(argv) > 2 else 12
+    min_log_h = int(argv[3]) if len(argv) > 3 else 5
     oracle = oracle_lib.Oracle()
     t0 = time.time()
-    for seed in range(first, first + count):
-        desc, n = one(oracle, seed, max_log_h, min_log_h)
+    agreed = 0
+    for seed in range(first, first + count):   # a mismatch is an AssertionError: the sweep ends at the first one
+        desc, n = one(oracle, seed, max_log_h, min_log_h, max_log_arity_4=la4)
+        agreed += 1
         print(f"ok  {desc}  ({n} B)", flush=True)
     print(f"{count} draws agree with the oracle byte for byte ({time.time() - t0:.0f} s)", flush=True)
+    if la4:
+        print(f"max_log_arity = 4: seeds {first}..{first + count - 1}, {count} draws, {count - agreed} mismatches, "
+              f"{FOLDED_BY_16[0]} proofs with a 16-ary commit phase, {FOLDED_BY_16[1]} refused by both sides", flush=True)
 
 
 if __name__ == "__main__":
