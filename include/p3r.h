@@ -303,6 +303,28 @@ int p3r_mmcs_open(p3r_ctx* ctx, const p3r_tree* tree, size_t index, uint32_t* op
                   uint32_t* proof_out);
 /* Digests of one opening proof of this tree (`Mmcs::Proof = Vec<[F; 8]>`). */
 size_t p3r_tree_proof_len(const p3r_tree* tree);
+/* The hiding MMCS at this seam (cfg.mmcs_salt_elems = S > 0; MerkleTreeHidingMmcs, recursion/src/pcs/mmcs.rs:315-413,
+ * :763-790).  p3r_mmcs_commit / p3r_mmcs_commit_dmat then draw one salt matrix (height_i x S, owned by the tree; with
+ * _dmat the caller's matrices stay borrowed) per committed matrix and commit [M0 | S0], [M1 | S1], ..  The salts come from
+ * the generator of zk_key at the context's proof counter, on a stream of their own: EVERY PUBLIC COMMIT ON A HIDING
+ * CONTEXT ADVANCES THE PROOF COUNTER (p3r_zk_nonce) BY ONE, as a proof does, so two commits of the same matrices give
+ * different caps and no commit shares a value with a proof; under P3R_EXT_ZK_DETERMINISTIC, p3r_zk_set_nonce makes a
+ * commit reproducible.  zk = 1 with mmcs_salt_elems = 0 stays a plain commit (HidingFriPcs runs over the non-hiding MMCS).
+ * p3r_tree_total_width stays the words of opened_values per index - the caller's widths, without the salts;
+ * p3r_tree_salt_elems is S (0: a plain tree) and p3r_tree_num_matrices the number of matrices the caller committed.
+ * p3r_mmcs_open has no salt output: on a hiding tree it returns P3R_EINVAL; open with p3r_mmcs_open_batch. */
+size_t p3r_tree_salt_elems(const p3r_tree* tree);
+size_t p3r_tree_num_matrices(const p3r_tree* tree);
+/* Mmcs::open_batch for each of `n` indices (any order, repeats allowed) in one gather launch, one copy back and one
+ * wait - what a PCS opens for its query indices.  For entry i: opened_values[i] = the rows in commit order, each matrix
+ * at its own scale (indices[i] >> (log_max_height - log_height)); salts[i] = the per-matrix salts in commit order - the
+ * first half of the hiding MMCS's opening proof `(salts, siblings)` (mmcs.rs:763-790), what p3r_mmcs_verify_salted takes;
+ * proofs[i] = the sibling digests as p3r_mmcs_open gives them.  Everything canonical.  n == 0: P3R_OK, nothing touched.
+ * An index >= 2^log_max_height, or salts == NULL on a hiding tree: P3R_EINVAL before anything is launched. */
+int p3r_mmcs_open_batch(p3r_ctx* ctx, const p3r_tree* tree, const size_t* indices, size_t n,
+                        uint32_t* opened_values, /* n x p3r_tree_total_width */
+                        uint32_t* salts,         /* n x num_matrices x salt_elems; may be NULL iff salt_elems == 0 */
+                        uint32_t* proofs);       /* n x p3r_tree_proof_len x 8 */
 /* Mmcs::verify_batch on the host, no context: heights / widths of the committed matrices in commit order, the opened
  * rows concatenated in that order, `proof` = proof_len digests.  Honours cfg->mmcs_arity (and, for arity 4, the
  * width-32 constants of cfg).  Returns P3R_OK when the opening is accepted, P3R_EINVAL with the reason in err_buf

@@ -205,6 +205,9 @@ SIGNATURES = {
     "p3r_tree_log_max_height": (C.c_size_t, [vp]),
     "p3r_tree_total_width": (C.c_size_t, [vp]),
     "p3r_tree_proof_len": (C.c_size_t, [vp]),
+    "p3r_tree_salt_elems": (C.c_size_t, [vp]),
+    "p3r_tree_num_matrices": (C.c_size_t, [vp]),
+    "p3r_mmcs_open_batch": (C.c_int, [vp, vp, C.POINTER(C.c_size_t), C.c_size_t, u32p, u32p, u32p]),
     "p3r_mmcs_verify": (C.c_int, [C.POINTER(P3rConfig), u32p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t,
                                   u32p, u32p, C.c_size_t, C.c_char_p, C.c_size_t]),
     "p3r_mmcs_verify_salted": (C.c_int, [C.POINTER(P3rConfig), u32p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t,

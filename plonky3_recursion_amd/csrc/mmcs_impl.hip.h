@@ -8,7 +8,8 @@
 //   mmcs_hash_rows_strided   the leaf digests of a FRI commit phase
 //   mmcs_cap_mont            the cap, downloaded
 //   mmcs_commit / mmcs_open  MerkleTreeMmcs::commit / open_batch over device matrices
-// The salts of a hiding MMCS are drawn by the callers (prove_impl.hip.h: they need a proof's key stream).
+//   mmcs_open_batch          open_batch for many indices (and the salts of a hiding tree): one launch, one copy back
+// The salts of a hiding MMCS are drawn by the callers (prove_impl.hip.h, p3r_core.hip: they need a key stream).
 
 namespace {
 
@@ -279,6 +280,94 @@ void mmcs_open(p3r_ctx* ctx, const p3r_tree* tree, size_t index, uint32_t* opene
   P3R_HIP(hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < off; ++i) opened[i] = F::raw(opened[i]).to_canonical();
   for (size_t i = 0; i < depth * P2_DIGEST; ++i) proof[i] = F::raw(proof[i]).to_canonical();
+}
+
+// Where the words of one opening come from: the same for every index of a call, only the position depends on the index.
+// One item per committed matrix, per salt matrix and per sibling slot; an index's block of the output is
+// [rows, total_width | salts, num_matrices x salt_elems | siblings, proof_len x 8] and the items are sorted by `dst`.
+struct OpenItem {
+  const uint32_t* base;  // a matrix (column-major) or a layer's digests ([8][layer_n])
+  uint64_t n;            // its height / layer_n: the words between consecutive elements of the item
+  uint32_t dst;          // first output word of the item inside an index's block
+  uint32_t shift;        // position = index >> shift (log_max_h - log_h of a matrix, the level's `bits` of a sibling)
+  uint32_t step, slot;   // siblings: children per node and which of its step - 1 siblings in ascending position, the
+                         // node's own left out; rows: step = 0
+};
+// One workgroup per index, its lanes over the words of that index's block.  Canonical output.
+template <class PP>
+__global__ void __launch_bounds__(256)
+k_mmcs_open_batch(const OpenItem* __restrict__ items, uint32_t n_items, const uint32_t* __restrict__ indices, uint32_t words,
+                  uint32_t* __restrict__ out) {
+  const uint32_t index = indices[blockIdx.x];
+  uint32_t* dst = out + (size_t)blockIdx.x * words;
+  for (uint32_t w = threadIdx.x; w < words; w += 256) {
+    uint32_t lo = 0, hi = n_items;  // the item of word w: the last one that begins at or before it
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (items[mid].dst <= w) lo = mid; else hi = mid;
+    }
+    const OpenItem it = items[lo];
+    size_t pos = index >> it.shift;
+    if (it.step) {
+      const size_t own = pos & (it.step - 1);
+      pos = pos - own + it.slot + (it.slot >= own ? 1 : 0);
+    }
+    dst[w] = Fp<PP>::raw(as_global(it.base)[(size_t)(w - it.dst) * it.n + pos]).to_canonical();
+  }
+}
+
+// Mmcs::open_batch for every index of `indices`: rows in commit order at each matrix's own scale, under a hiding tree the
+// per-matrix salts in commit order, the siblings bottom-up as mmcs_open gives them.  One gather launch into one device
+// buffer, one copy back, one wait.  opened: n x total_width, salts: n x num_matrices x salt_elems, proofs: n x proof_len x 8.
+template <class PP>
+void mmcs_open_batch(p3r_ctx* ctx, const p3r_tree* tree, const size_t* indices, size_t n, uint32_t* opened, uint32_t* salts,
+                     uint32_t* proofs) {
+  if (tree->log_max_h > 31) fail(P3R_EUNSUPPORTED, "open_batch of a tree of 2^%d rows", tree->log_max_h);
+  std::vector<uint32_t> idx32(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (indices[i] >> tree->log_max_h) fail(P3R_EINVAL, "open index %zu (entry %zu) out of range", indices[i], i);
+    idx32[i] = (uint32_t)indices[i];
+  }
+  const size_t S = (size_t)tree->salt_elems, per = S ? 2 : 1, n_mats = tree->mats.size() / per;
+  const size_t w_rows = tree->total_width, w_salts = n_mats * S, w_proof = mmcs_proof_len(tree->levels) * P2_DIGEST;
+  const size_t words = w_rows + w_salts + w_proof;
+  if (words >> 31 || n >> 31) fail(P3R_EUNSUPPORTED, "open_batch of %zu indices of %zu words each", n, words);
+  std::vector<OpenItem> items;
+  size_t off = 0;
+  for (size_t i = 0; i < n_mats; ++i) {
+    const p3r_dmat* m = tree->mats[i * per];
+    const uint32_t shift = (uint32_t)(tree->log_max_h - log2_exact(m->h, "matrix height"));
+    if (m->w) items.push_back(OpenItem{m->d, m->h, (uint32_t)off, shift, 0, 0});
+    off += m->w;
+    if (S) items.push_back(OpenItem{tree->mats[i * per + 1]->d, m->h, (uint32_t)(w_rows + i * S), shift, 0, 0});
+  }
+  off = w_rows + w_salts;
+  const size_t last = (size_t(1) << tree->log_max_h) - 1;
+  for (size_t l = 0; l < tree->levels.size(); ++l) {
+    const MmcsLevel& lv = tree->levels[l];
+    if (((last >> lv.bits) | (size_t)(lv.step - 1)) >= tree->layer_n[l]) fail(P3R_EHIP, "internal: Merkle layer %zu shorter than its level", l);
+    for (int j = 0; j + 1 < lv.step; ++j, off += P2_DIGEST)
+      items.push_back(OpenItem{tree->layers[l].p, tree->layer_n[l], (uint32_t)off, (uint32_t)lv.bits, (uint32_t)lv.step, (uint32_t)j});
+  }
+  if (!words) return;
+  std::stable_sort(items.begin(), items.end(), [](const OpenItem& a, const OpenItem& b) { return a.dst < b.dst; });
+  DevBuf d_items((items.size() * sizeof(OpenItem) + 3) / 4), d_idx(n), d_out(n * words);
+  P3R_HIP(ctx->stage.upload(ctx->stream, d_items.p, items.data(), items.size() * sizeof(OpenItem)));
+  P3R_HIP(ctx->stage.upload(ctx->stream, d_idx.p, idx32.data(), n * 4));
+  {
+    ProfScope ps(ctx, "mmcs_open_batch");
+    hipLaunchKernelGGL(k_mmcs_open_batch<PP>, dim3((unsigned)n), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const OpenItem*>(d_items.p), (uint32_t)items.size(), d_idx.p, (uint32_t)words, d_out.p);
+    P3R_HIP(hipGetLastError());
+  }
+  const uint32_t* got = nullptr;
+  P3R_HIP(ctx->landing.fetch(ctx->stream, d_out.p, n * words * 4, &got));
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t* g = got + i * words;
+    std::memcpy(opened + i * w_rows, g, w_rows * 4);
+    if (w_salts) std::memcpy(salts + i * w_salts, g + w_rows, w_salts * 4);
+    std::memcpy(proofs + i * w_proof, g + w_rows + w_salts, w_proof * 4);
+  }
 }
 
 }  // namespace

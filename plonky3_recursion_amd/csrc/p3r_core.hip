@@ -257,10 +257,23 @@ void init_ctx(p3r_ctx* ctx) {
 #include "circuit_impl.hip.h"
 
 namespace {
-// MMCS commit as the ABI hands the cap out: canonical
+// MMCS commit as the ABI hands the cap out: canonical.  Under a hiding MMCS (p3r_config.mmcs_salt_elems > 0) the tree
+// commits [M0, S0, M1, S1, ..] as the prover's trees do (commit_dmats), with salts of its own: the key of the next proof
+// counter value - a public commit takes one, as a proof does - on a stream round no proof draws from.
 template <class PP>
 void mmcs_commit_canonical(p3r_ctx* ctx, p3r_tree* tree, uint32_t* cap_out) {
+  const size_t S = ctx->cfg.mmcs_salt_elems, n_mats = tree->mats.size();
+  if (S) {
+    const std::vector<const p3r_dmat*> mats = tree->mats;
+    for (const p3r_dmat* m : mats) log2_exact(m->h, "matrix height");
+    const ZkKey key = zk_key_of(ctx, ctx->zk_nonce++);
+    tree->salt_elems = (int)S;
+    tree->salt_owned = draw_salts<PP>(ctx, mats, kSaltRound + ZK_ROUND_PUBLIC_COMMIT, key);
+    tree->mats.clear();
+    for (size_t i = 0; i < n_mats; ++i) { tree->mats.push_back(mats[i]); tree->mats.push_back(tree->salt_owned[i].get()); }
+  }
   const std::vector<uint32_t> cap = mmcs_commit<PP>(ctx, tree);
+  tree->total_width -= n_mats * S;  // words of opened_values per index: the caller's widths, without the salts
   for (size_t i = 0; i < cap.size(); ++i) cap_out[i] = Fp<PP>::raw(cap[i]).to_canonical();
 }
 }  // namespace
@@ -577,9 +590,22 @@ int p3r_mmcs_open(p3r_ctx* ctx, const p3r_tree* tree, size_t index, uint32_t* op
                   uint32_t* proof_out) {
   return guard(ctx, [&] {
     if (!tree || !opened_values || !proof_out) fail(P3R_EINVAL, "NULL argument");
+    if (tree->salt_elems) fail(P3R_EINVAL, "p3r_mmcs_open has no salt output: open a hiding tree with p3r_mmcs_open_batch");
     P3R_FIELD_CALL(ctx, mmcs_open, ctx, tree, index, opened_values, proof_out);
   });
 }
+int p3r_mmcs_open_batch(p3r_ctx* ctx, const p3r_tree* tree, const size_t* indices, size_t n, uint32_t* opened_values,
+                        uint32_t* salts, uint32_t* proofs) {
+  return guard(ctx, [&] {
+    if (!tree) fail(P3R_EINVAL, "tree is NULL");
+    if (n == 0) return;
+    if (!indices || !opened_values || !proofs) fail(P3R_EINVAL, "NULL argument");
+    if (tree->salt_elems && !salts) fail(P3R_EINVAL, "salts is NULL: the openings of a hiding tree carry %d salt elements per matrix", tree->salt_elems);
+    P3R_FIELD_CALL(ctx, mmcs_open_batch, ctx, tree, indices, n, opened_values, salts, proofs);
+  });
+}
+size_t p3r_tree_salt_elems(const p3r_tree* t) { return (size_t)t->salt_elems; }
+size_t p3r_tree_num_matrices(const p3r_tree* t) { return t->mats.size() / (t->salt_elems ? 2 : 1); }
 size_t p3r_tree_log_max_height(const p3r_tree* t) { return (size_t)t->log_max_h; }
 size_t p3r_tree_total_width(const p3r_tree* t) { return t->total_width; }
 size_t p3r_tree_proof_len(const p3r_tree* t) { return p3r::mmcs_proof_len(t->levels); }

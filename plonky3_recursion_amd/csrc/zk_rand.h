@@ -22,7 +22,11 @@
 
 namespace p3r {
 
-enum { ZK_ROUND_RANDOM = 0, ZK_ROUND_MAIN = 1, ZK_ROUND_QUOTIENT = 2, ZK_ROUND_PREP = 3, ZK_ROUND_PERM = 4, ZK_ROUND_QMASK = 5 };
+enum { ZK_ROUND_RANDOM = 0, ZK_ROUND_MAIN = 1, ZK_ROUND_QUOTIENT = 2, ZK_ROUND_PREP = 3, ZK_ROUND_PERM = 4, ZK_ROUND_QMASK = 5,
+       // the salts of a commit through the public MMCS entry points (p3r_mmcs_commit / _dmat) and nothing else: a public
+       // commit and a proof never share a value, even at the same nonce.  (7, not 6: kSaltRound + 6 is kSaltRoundFri;
+       // kSaltRound + 7 = 15 is the last round a stream id has room for below the fallback bits.)
+       ZK_ROUND_PUBLIC_COMMIT = 7 };
 // salts of a hiding MMCS (p3r_config.mmcs_salt_elems): stream round kSaltRound + the round of the committed batch, matrix =
 // its position in the batch; kSaltRoundFri for the FRI commit-phase trees (matrix = phase)
 constexpr int kSaltRound = 8, kSaltRoundFri = 14;

@@ -479,8 +479,34 @@ class MerkleTree:
     def log_max_height(self):
         return self.ctx.lib.p3r_tree_log_max_height(self.h)
 
+    @property
+    def salt_elems(self):
+        """Salt elements per committed row (0: a plain tree)."""
+        return self.ctx.lib.p3r_tree_salt_elems(self.h)
+
+    @property
+    def num_matrices(self):
+        """Matrices the caller committed (the salt matrices of a hiding tree are not counted)."""
+        return self.ctx.lib.p3r_tree_num_matrices(self.h)
+
+    def open_many(self, indices):
+        """Mmcs::open_batch for every index in one launch (p3r_mmcs_open_batch).  Returns (opened[n, total_width],
+        salts[n, num_matrices, salt_elems] or None for a plain tree, proofs[n, depth, 8])."""
+        lib = self.ctx.lib
+        idx = [int(i) for i in indices]
+        n, S = len(idx), self.salt_elems
+        opened = np.empty((n, lib.p3r_tree_total_width(self.h)), dtype=np.uint32)
+        salts = np.empty((n, self.num_matrices, S), dtype=np.uint32) if S else None
+        proofs = np.empty((n, lib.p3r_tree_proof_len(self.h), 8), dtype=np.uint32)
+        arr = (C.c_size_t * max(n, 1))(*idx)
+        self.ctx.check(lib.p3r_mmcs_open_batch(self.ctx.h, self.h, arr, n, opened.ctypes.data_as(_lib.u32p),
+                                               salts.ctypes.data_as(_lib.u32p) if S else None,
+                                               proofs.ctypes.data_as(_lib.u32p)))
+        return opened, salts, proofs
+
     def open_batch(self, index):
-        """Returns (opened_values concatenated in commit order, proof[(depth, 8)])."""
+        """Returns (opened_values concatenated in commit order, proof[(depth, 8)]).  A hiding tree (salt_elems > 0) is
+        opened with open_many: this form has no salt output and raises the library's error there."""
         w = self.ctx.lib.p3r_tree_total_width(self.h)
         depth = self.ctx.lib.p3r_tree_proof_len(self.h)   # binary: log_max_height - cap_height; arity 4: sum of (step - 1)
         opened = np.empty(w, dtype=np.uint32)
