@@ -81,8 +81,10 @@ P3R_HD double p2f_mul_2exp_neg(double x, double m) {
   const double f = p2f_fract(t);
   return __builtin_fma(-f, P2F64<PP>::P, t);
 }
-// x * m + a mod P for k <= 8 and an INTEGER a with |a| < 2^40: the addend rides in the first FMA
-// (a + x * 2^-k has at most 40 + 8 significant bits, so it is exact and frac(t) is unchanged)
+// x * m + a mod P for an INTEGER a: the addend rides in the first FMA, which is exact while |x| + 2^k |a| < 2^53 (the
+// value in units of 2^-k; frac(t) is then the fraction of x * 2^-k alone).  |result| < |x| / 2^k + |a| + P.  The only
+// caller is the width-32 kernel, with k <= 12: p2wf_partial_walk (poseidon2_w32_f64.hip.h) checks that precondition and
+// the fixed value's bound at every round of its schedule.
 template <class PP>
 P3R_HD double p2f_mul_2exp_neg_add(double x, double m, double a) {
   const double t = __builtin_fma(x, m, a);

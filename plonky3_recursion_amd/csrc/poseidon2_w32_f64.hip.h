@@ -1,7 +1,9 @@
-// Poseidon2 width-32 permutation in FP64, device only: the throughput form of the arity-4 MMCS
+// Poseidon2 width-32 permutation in FP64: the throughput form of the arity-4 MMCS
 // (PaddingFreeSponge<Perm32, 32, 24, 8> leaves, TruncatedPermutation<Perm32, 4, 8, 32> levels; one permutation per
 // lane).  Same representation and building blocks as the width-16 form (poseidon2_f64.hip.h: a state element is a
-// double holding an integer congruent to the canonical value, only the S-box reduces in the full rounds).
+// double holding an integer congruent to the canonical value, only the S-box reduces in the full rounds).  The arithmetic
+// also builds on the host (P3R_HD; tools/microbench/host_p2wf_check.cpp compares it with the integer permutation of
+// poseidon2.h there).
 //
 // What differs from width 16: the internal diagonal is the caller's DATA (p3r_config.poseidon2_w32_diag), so its
 // entries are general field elements and, in general, a partial round multiplies every lane by its entry with a full
@@ -25,9 +27,10 @@
 // round and every chain runs at FP64 latency.  profiles/r05/w32_diag_ab.txt.)
 //
 // Magnitudes: inputs |x| <= P (fresh cells, or carried lanes that p2wf_permute reduces on the way in).  External layer: rows of
-// circ(2 M4, M4, ..) sum to 7 * 9 = 63, so a full round's S-box sees |x| < 63 * 1.3 P + P < 2^38 - inside the domain
-// of the narrow S-box (p2f_mulmod_k needs |a b| < 2^76).  Partial rounds: d_i * s_i reduced to < 0.7 P, the lane sum
-// reduced to <= 0.5 P: no growth.
+// circ(2 M4, M4, ..) sum to 7 * 9 = 63, so a full round's S-box sees |x| <= 63 max(P, 0.7 P) + P < 2^38 - inside the domain
+// of the narrow S-box (p2f_mulmod_k needs |a b| < 2^76).  Partial rounds, general diagonal: d_i * s_i reduced to < 0.7 P,
+// the lane sum reduced to <= 0.5 P: no growth (p2wf_general_check below).  Built-in diagonal: the lanes grow between
+// scheduled reductions; p2wf_partial_walk below walks the schedule.  Both are static_asserted for both fields.
 #pragma once
 #include <utility>
 
@@ -38,7 +41,7 @@ namespace p3r {
 
 #pragma clang fp contract(off)
 
-__device__ __forceinline__ void p2wf_external_linear(double* s) {
+P3R_HD void p2wf_external_linear(double* s) {
 #pragma unroll
   for (int i = 0; i < P2W_WIDTH; i += 4) p2f_mat4(s[i], s[i + 1], s[i + 2], s[i + 3]);
   double sum[4];
@@ -59,10 +62,13 @@ __device__ __forceinline__ void p2wf_external_linear(double* s) {
 // them in front of every use), `p_hi` = P_HI and the diagonal entry in scalar register pairs (one scalar operand per
 // instruction on gfx9).
 // No per-entry d / P: the quotient comes from (a / P) * d - one more multiplication (six instructions) and 64 fewer
-// vector registers than round 4's five-instruction form with c = d / P per entry.  (a * INVP) * d carries two roundings instead of one: an error
-// below 2^-20 on a quotient below 2^32, so q is still within one of the exact quotient's rounding and |result| < 0.7 P.
+// vector registers than round 4's five-instruction form with c = d / P per entry.  (a * INVP) * d carries two roundings instead of one
+// (INVP and the product a * INVP, 2^-53 relative each) in front of the FMA's rounding to an integer.  The largest quotient
+// is the first partial round's, where lanes 1..31 arrive from the external layer at 63 * 0.7 P (2^36.4) and |d| <= P / 2:
+// |q| < 2^36, the two roundings move it by less than 2^-15, so q is the rounding of a value within 2^-15 of a d / P and
+// |a d - q P| < 0.7 P.  p2wf_general_check asserts this and the other steps' ranges at that worst case.
 template <class PP>
-__device__ __forceinline__ double p2f_mulmod_s_add(double a, double d, double addM, double magic, double neg_c, double p_hi) {
+P3R_HD double p2f_mulmod_s_add(double a, double d, double addM, double magic, double neg_c, double p_hi) {
   const double ai = a * P2F64<PP>::INVP;
   const double qm = __builtin_fma(ai, d, magic);
   const double t = __builtin_fma(qm, p_hi, neg_c);
@@ -72,7 +78,7 @@ __device__ __forceinline__ double p2f_mulmod_s_add(double a, double d, double ad
 
 // s_i <- d_i s_i + sum(s)
 template <class PP>
-__device__ __forceinline__ void p2wf_internal_linear(double* s, const double* d, double magic, double neg_c, double p_hi) {
+P3R_HD void p2wf_internal_linear(double* s, const double* d, double magic, double neg_c, double p_hi) {
   double part[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k)
@@ -129,18 +135,20 @@ constexpr bool p2w_default_inline(int i) {
   return a == 0.5 || a == 1.0 || a == 2.0 || a == 4.0;
 }
 template <class PP, int I>
-__device__ __forceinline__ void p2wf_pin_default(double* mk) {
+P3R_HD void p2wf_pin_default(double* mk) {
   if constexpr (p2w_default_rep<PP>(I) == I && !p2w_default_inline<PP>(I)) {
     constexpr double mag = p2w_abs(p2w_default_factor<PP>(I));
     mk[I] = mag;
+#if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+s"(mk[I]));
+#endif
   }
 }
 template <class PP, int... I>
-__device__ __forceinline__ void p2wf_pin_defaults(double* mk, std::integer_sequence<int, I...>) { (p2wf_pin_default<PP, I>(mk), ...); }
+P3R_HD void p2wf_pin_defaults(double* mk, std::integer_sequence<int, I...>) { (p2wf_pin_default<PP, I>(mk), ...); }
 
 template <class PP, int I>
-__device__ __forceinline__ void p2wf_lane_default(double* s, const double* mk, double sum) {
+P3R_HD void p2wf_lane_default(double* s, const double* mk, double sum) {
   constexpr P2WLaneForm f = p2w_default_form<PP>(I);
   static_assert(f.form != 3, "the built-in width-32 diagonal is made of small integers and inverse powers of two");
   // (constexpr variables, not calls: a call outside a constant expression is compiled, and the 64-bit `%` loops of these
@@ -154,25 +162,39 @@ __device__ __forceinline__ void p2wf_lane_default(double* s, const double* mk, d
   else s[I] = p2f_mul_2exp_neg<PP>(s[I], m) + sum;
 }
 // `period` names the growth class of a small-integer lane: 5 = |d| in 2..4, 4 = |d| in 5..7, 3 = |d| in 8..16
+// The rounds at whose start a class is reduced - the ONE statement of the schedule: p2wf_internal_linear_default runs it,
+// p2wf_partial_walk checks it.  A lane multiplied by a small integer grows by that factor every round, from 63 * 0.7 P
+// (2^36.4) at the first round and from P / 2 after a reduction: |d| <= 4 reduced at the start of rounds 5, 13, 21, 29
+// (4^5 2^36.4, then 4^8 2^30), |d| <= 7 at 3, 8, 13, .. (7^3, then 7^5), |d| <= 16 at 2, 5, 8, .. (16^2, then 16^3).
+// (Before that schedule: every 5 / 4 / 3 rounds from round 0.)
+// (Statements, not one `?:` expression: inlined with a constant `period`, this form leaves the kernel's three branches as
+// the conditions written in place did - the same instructions - while a value-returning chain compiled to selects and
+// moved the register allocation of the whole round.)
+constexpr bool p2wf_reduce_round(int period, int r) {
+  if (period == 5) { if (r >= 5 && (r - 5) % 8 == 0) return true; }
+  else if (period == 4) { if (r >= 3 && (r - 3) % 5 == 0) return true; }
+  else if (period == 3) { if (r >= 2 && (r - 2) % 3 == 0) return true; }
+  return false;
+}
 template <class PP, int PERIOD, int I>
-__device__ __forceinline__ void p2wf_lane_reduce(double* s) {
+P3R_HD void p2wf_lane_reduce(double* s) {
   if constexpr (I > 0 && p2w_default_form<PP>(I).period == PERIOD) s[I] = p2f_reduce<PP>(s[I]);   // lane 0: the S-box reduces it
 }
+// the lanes reduced once more after the last partial round (p2wf_reduce_grown): the small-integer lanes that grow
+template <class PP>
+constexpr bool p2wf_lane_grown(int i) { return i > 0 && p2w_default_form<PP>(i).period > 0; }
 template <class PP, int I>
-__device__ __forceinline__ void p2wf_lane_reduce_grown(double* s) {
-  if constexpr (I > 0 && p2w_default_form<PP>(I).period > 0) s[I] = p2f_reduce<PP>(s[I]);
+P3R_HD void p2wf_lane_reduce_grown(double* s) {
+  if constexpr (p2wf_lane_grown<PP>(I)) s[I] = p2f_reduce<PP>(s[I]);
 }
 template <class PP, int... I>
-__device__ __forceinline__ void p2wf_reduce_grown(double* s, std::integer_sequence<int, I...>) { (p2wf_lane_reduce_grown<PP, I>(s), ...); }
+P3R_HD void p2wf_reduce_grown(double* s, std::integer_sequence<int, I...>) { (p2wf_lane_reduce_grown<PP, I>(s), ...); }
 template <class PP, int... I>
-__device__ __forceinline__ void p2wf_internal_linear_default(double* s, const double* mk, int r, std::integer_sequence<int, I...>) {
-  // A lane multiplied by a small integer grows by that factor every round, from < 2^37 (63 * 0.7 P) at the first round and
-  // from 2^30 after a reduction; kept below 2^47, so that the sum of all of them stays below 2^51: |d| <= 4 reduced at the
-  // start of rounds 5, 13, 21, 29 (4^5 2^36.4, then 4^8 2^30), |d| <= 7 at 3, 8, 13, .. (7^3, then 7^5), |d| <= 16 at 2, 5, 8, ..
-  // (16^2, then 16^3).  (Until this change: every 5 / 4 / 3 rounds from round 0.)
-  if (r >= 5 && (r - 5) % 8 == 0) (p2wf_lane_reduce<PP, 5, I>(s), ...);
-  if (r >= 3 && (r - 3) % 5 == 0) (p2wf_lane_reduce<PP, 4, I>(s), ...);
-  if (r >= 2 && (r - 2) % 3 == 0) (p2wf_lane_reduce<PP, 3, I>(s), ...);
+P3R_HD void p2wf_internal_linear_default(double* s, const double* mk, int r, std::integer_sequence<int, I...>) {
+  // p2wf_partial_walk: every lane, the 32-lane sum and each of its partial sums stay integers below 2^53 on this schedule
+  if (p2wf_reduce_round(5, r)) (p2wf_lane_reduce<PP, 5, I>(s), ...);
+  if (p2wf_reduce_round(4, r)) (p2wf_lane_reduce<PP, 4, I>(s), ...);
+  if (p2wf_reduce_round(3, r)) (p2wf_lane_reduce<PP, 3, I>(s), ...);
   double part[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k)
@@ -181,14 +203,151 @@ __device__ __forceinline__ void p2wf_internal_linear_default(double* s, const do
   (p2wf_lane_default<PP, I>(s, mk, sum), ...);
 }
 
+// ---- the bound walkers: the partial rounds on worst-case magnitudes, step by step (p2f_partial_walk is the width-16 one)
+//
+// The bound a caller may rely on for every output lane, and the largest magnitude a CARRIED lane may hold: the last full
+// round leaves 63 * 0.7 P (the external layer over S-box outputs); stated with the slack the kernels' comments have
+// always given it.  Checked below against what the rounds really leave, against p2f_store (< 2^40) and against the
+// carried lane's p2f_reduce (an integer below 2^53).
+template <class PP>
+constexpr unsigned long long p2wf_out_bound() { return 63ull * ((13ull * PP::P + 9) / 10); }
+
+// the built-in diagonal's entry as a centred integer, and k for an entry +-2^-k (0: not one)
+template <class PP>
+constexpr long long p2w_default_centred(int i) {
+  const uint32_t d = PP::FIELD_ID == 0 ? kDefaultDiagW32_koala_bear[i] : kDefaultDiagW32_baby_bear[i];
+  return d > PP::P / 2 ? (long long)d - (long long)PP::P : (long long)d;
+}
+template <class PP>
+constexpr int p2w_default_k(int i) {
+  const uint32_t d = PP::FIELD_ID == 0 ? kDefaultDiagW32_koala_bear[i] : kDefaultDiagW32_baby_bear[i];
+  for (int k = 1; k <= PP::TWO_ADICITY; ++k) {
+    const uint64_t t = ((uint64_t)d << k) % PP::P;
+    if (t == 1 || t == PP::P - 1) return k;
+  }
+  return 0;
+}
+
+// Built-in diagonal (p2wf_internal_linear_default, then p2wf_reduce_grown).  Per lane a bound M >= |x|; every lane is an
+// integer at every lane sum (the +-2^-k lanes are fixed in the round that divides them).  What it checks:
+//   full rounds      63 max(P, 0.7 P) + P < 2^38: every S-box of the full rounds is inside the narrow S-box's domain;
+//   lane 0           |x + rc| < 2^38 at the S-box of every partial round;
+//   p2f_reduce       on the rounds of p2wf_reduce_round: the input is an integer below 2^53, the output <= P / 2 + 1;
+//   the lane sum     the sum of the 32 bounds is below 2^53, so the sum and every partial sum, in any order, are exact;
+//   form 0           |d| M + S < 2^53;
+//   form 1           fma(x, 2^-k, sum) is exact: M + 2^k S < 2^53 (in units of 2^-k), k <= min(12, TWO_ADICITY); the fixed
+//                    value is below M / 2^k + S + P;
+//   form 2           k <= TWO_ADICITY; x 2^-k is exact (a power of two); the fixed value M / 2^k + P, plus S, below 2^53;
+//   the exit         after p2wf_reduce_grown every lane is below 2^38 - P;
+//   the outputs      63 * 0.7 P <= p2wf_out_bound < 2^40 (p2f_store), < 2^53 (a carried lane's p2f_reduce).
+// Returns 0, or 1000 (round + 1) + 10 lane + step (1 .. 9), 100000 + 10 lane + step after the rounds, 1 / 2 before them.
+template <class PP>
+constexpr int p2wf_partial_walk() {
+  using u64 = unsigned long long;
+  constexpr u64 EXACT = u64(1) << 53, SBOX_IN = u64(1) << 38, P = PP::P;
+  constexpr u64 SBOX_OUT = (7 * P + 9) / 10, RED = P / 2 + 2;
+  if (63 * SBOX_OUT + P >= SBOX_IN) return 1;
+  if (63 * P + P >= SBOX_IN) return 2;   // the first full round: inputs <= P
+  u64 M[P2W_WIDTH] = {};
+  for (int i = 0; i < P2W_WIDTH; ++i) M[i] = 63 * SBOX_OUT;
+  for (int r = 0; r < PP::PARTIAL_ROUNDS_W32; ++r) {
+    const int at = 1000 * (r + 1);
+    if (M[0] + (P - 1) >= SBOX_IN) return at + 1;
+    M[0] = SBOX_OUT;
+    for (int i = 1; i < P2W_WIDTH; ++i) {   // p2wf_lane_reduce: lane 0 is the S-box's
+      const P2WLaneForm f = p2w_default_form<PP>(i);
+      if (f.period > 0 && p2wf_reduce_round(f.period, r)) {
+        if (M[i] >= EXACT) return at + 10 * i + 2;
+        M[i] = RED;
+      }
+    }
+    u64 T = 0;
+    for (int i = 0; i < P2W_WIDTH; ++i) T += M[i];   // (32 terms below 2^53 each: no wrap before the test)
+    if (T >= EXACT) return at + 3;
+    const u64 S = RED;
+    for (int i = 0; i < P2W_WIDTH; ++i) {
+      const P2WLaneForm f = p2w_default_form<PP>(i);
+      const long long c = p2w_default_centred<PP>(i);
+      const int k = p2w_default_k<PP>(i);
+      if (f.form == 0) {
+        M[i] = u64(c < 0 ? -c : c) * M[i] + S;
+        if (M[i] >= EXACT) return at + 10 * i + 4;
+      } else if (f.form == 1) {
+        if (k < 1 || k > 12 || k > PP::TWO_ADICITY) return at + 10 * i + 5;
+        if (M[i] + (S << k) >= EXACT) return at + 10 * i + 6;
+        M[i] = ((M[i] + (u64(1) << k) - 1) >> k) + S + P;
+        if (M[i] >= EXACT) return at + 10 * i + 7;
+      } else if (f.form == 2) {
+        if (k < 1 || k > PP::TWO_ADICITY) return at + 10 * i + 8;
+        M[i] = ((M[i] + (u64(1) << k) - 1) >> k) + P + S;
+        if (M[i] >= EXACT) return at + 10 * i + 9;
+      } else {
+        return at + 10 * i;
+      }
+    }
+  }
+  for (int i = 0; i < P2W_WIDTH; ++i) {
+    if (p2wf_lane_grown<PP>(i)) {
+      if (M[i] >= EXACT) return 100000 + 10 * i + 1;
+      M[i] = RED;
+    }
+    if (M[i] + (P - 1) >= SBOX_IN) return 100000 + 10 * i + 2;
+  }
+  if (63 * SBOX_OUT > p2wf_out_bound<PP>()) return 100003;
+  if (p2wf_out_bound<PP>() >= (u64(1) << 40)) return 100004;   // p2f_store
+  if (p2wf_out_bound<PP>() >= EXACT) return 100005;             // a carried lane's p2f_reduce
+  return 0;
+}
+static_assert(p2wf_partial_walk<KoalaBearParams>() == 0, "KoalaBear: the width-32 partial-round schedule leaves exact FP64 arithmetic");
+static_assert(p2wf_partial_walk<BabyBearParams>() == 0, "BabyBear: the width-32 partial-round schedule leaves exact FP64 arithmetic");
+
+// General diagonal (p2f_mulmod_s_add in p2wf_internal_linear) at its worst case: the first partial round, where lanes 1..31
+// arrive from the external layer at 63 * 0.7 P, and |d| <= P / 2 (the table holds centred entries).  What it checks:
+//   1  |a d| < 2^76;
+//   2  the quotient: (a * INVP) * d carries two relative roundings of 2^-53 (INVP, and the product a * INVP) in front of the
+//      FMA, which rounds MAGIC + that to an integer: the two move the value by less than |a d / P| 2^-51, which must be
+//      below 1/2 -
+//   3  - and in fact below 1/8, so that |a d - q P| < (1/2 + 1/8) P < 0.7 P;
+//   4  MAGIC + q lies in [2^52, 2^53), where doubles are the integers: |q| < 2^51;
+//   5  q * P_HI is a double: |q| (P_HI / 2^TWO_ADICITY) < 2^53;
+//   6  e = (a d - q P) + q is an integer below 2^53;
+//   7  e + addM = e + sum + MAGIC and MAGIC + q are integers below 2^53;
+//   8  the lane leaves below 0.7 P + P / 2 + 2, no larger than it came: later rounds are inside this case;
+//   9  the 32-lane sum of the first round is below 2^53;
+//   10 lane 0 at the next S-box, and every lane at the full rounds after, below 2^38 - P.
+// Returns 0 or the number of the first step that fails.
+template <class PP>
+constexpr int p2wf_general_check() {
+  using u64 = unsigned long long;
+  using u128 = unsigned __int128;
+  constexpr u64 EXACT = u64(1) << 53, SBOX_IN = u64(1) << 38, P = PP::P, MAGIC = u64(3) << 51;
+  constexpr u64 SBOX_OUT = (7 * P + 9) / 10, RED = P / 2 + 2;
+  constexpr u64 A = 63 * SBOX_OUT, D = P / 2;
+  constexpr u128 AD = (u128)A * D;
+  if (AD >> 76) return 1;
+  constexpr u64 Q = (u64)(AD / P) + 2;   // > |a d / P| + 1 >= |q|
+  if (Q >= (u64(1) << 50)) return 2;
+  if (Q >= (u64(1) << 48)) return 3;
+  if (Q >= (u64(1) << 51)) return 4;
+  if ((u128)Q * ((P - 1) >> PP::TWO_ADICITY) >= EXACT) return 5;
+  if (SBOX_OUT + Q >= EXACT) return 6;
+  if (MAGIC + SBOX_OUT + Q + RED >= EXACT) return 7;
+  if (SBOX_OUT + RED > A) return 8;
+  if (SBOX_OUT + 31 * A >= EXACT) return 9;
+  if (SBOX_OUT + RED + (P - 1) >= SBOX_IN) return 10;
+  return 0;
+}
+static_assert(p2wf_general_check<KoalaBearParams>() == 0, "KoalaBear: p2f_mulmod_s_add leaves exact FP64 arithmetic at the first partial round's magnitudes");
+static_assert(p2wf_general_check<BabyBearParams>() == 0, "BabyBear: p2f_mulmod_s_add leaves exact FP64 arithmetic at the first partial round's magnitudes");
+
 // BUILTIN: the configured diagonal is the built-in one (its own kernel instance: the general path keeps 64 constants in
 // vector registers and runs at one wave per SIMD; this one needs none)
 // In: integers in [0, P] (p2f_load), except the lanes of CARRIED (bit i = lane i): unreduced outputs of a previous
-// permutation, reduced here (poseidon2_f64.hip.h: p2f_permute).  Out: |.| < 63 * 1.3 P, NOT reduced: a digest goes through
+// permutation (|.| <= p2wf_out_bound), reduced here (poseidon2_f64.hip.h: p2f_permute).  Out: |.| <= p2wf_out_bound, NOT reduced: a digest goes through
 // p2f_store, which reduces; a carried lane is reduced by the next permutation.  (Until round 5 all 32 outputs were reduced
 // on the way out: 96 instructions, 72 of them on lanes that were overwritten or dropped.)
 template <class PP, bool BUILTIN, unsigned CARRIED = 0xFFFFFFFFu>
-__device__ __forceinline__ void p2wf_permute(double* s, const double* __restrict__ tab) {
+P3R_HD void p2wf_permute(double* s, const double* __restrict__ tab) {
 #pragma unroll
   for (int i = 0; i < P2W_WIDTH; ++i)
     if (CARRIED >> i & 1u) s[i] = p2f_reduce<PP>(s[i]);
@@ -222,12 +381,16 @@ __device__ __forceinline__ void p2wf_permute(double* s, const double* __restrict
 #pragma unroll
     for (int i = 0; i < P2W_WIDTH; ++i) {
       dv[i] = d[i];
+#if defined(__HIP_DEVICE_COMPILE__)
       asm volatile("" : "+s"(dv[i]));
+#endif
     }
     double neg_c = -(P2F64<PP>::MAGIC * P2F64<PP>::P_HI);
     double magic = P2F64<PP>::MAGIC;
     double p_hi = P2F64<PP>::P_HI;
+#if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(neg_c), "+v"(magic), "+s"(p_hi));
+#endif
 #pragma unroll 1
     for (int r = 0; r < PP::PARTIAL_ROUNDS_W32; ++r) {
       s[0] = p2f_sbox<PP>(s[0] + tab[k + r], SK);

@@ -2,6 +2,7 @@
 // -DP3R_TUNING_KNOBS: what tests and tuning tools load); the product library neither compiles nor exports it.
 // Host arrays in, host arrays out, on the context's stream and pool.  tests/test_gpu_device_prims.py.
 #include "device_prims.hip.h"
+#include "test_seam.h"
 
 namespace p3r {
 namespace {
@@ -9,22 +10,6 @@ struct LoadU64 {
   const uint64_t* p;
   __device__ uint64_t operator()(size_t i) const { return p[i]; }
 };
-template <class Fn>
-int seam(p3r_ctx* ctx, Fn&& fn) {
-  try {
-    if (!ctx) return P3R_EINVAL;
-    (void)hipSetDevice(ctx->cfg.device);
-    tls_pool() = ctx->pool;
-    fn();
-    return P3R_OK;
-  } catch (const Error& e) {
-    ctx->err = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    ctx->err = e.what();
-    return P3R_EINVAL;
-  }
-}
 }  // namespace
 }  // namespace p3r
 

@@ -64,6 +64,51 @@ def test_commit_and_open_vs_oracle(oracle, field, shapes):
     c.close()
 
 
+def edge_matrices(field, h, w):
+    """All-zero, all P - 1, alternating 0 / P - 1 by column and by row."""
+    top = P[field] - 1
+    by_col, by_row = np.zeros((h, w), dtype=np.uint32), np.zeros((h, w), dtype=np.uint32)
+    by_col[:, 1::2] = top
+    by_row[1::2, :] = top
+    return [np.zeros((h, w), dtype=np.uint32), np.full((h, w), top, dtype=np.uint32), by_col, by_row]
+
+
+@pytest.mark.parametrize("field", FIELDS)
+@pytest.mark.parametrize("general", [False, True])
+def test_commit_edge_words(oracle, field, general):
+    """p2f_load and the width-32 sponge's `rem` branches on edge words: widths around the rate (24) and twice the rate, one
+    row and one wavefront of rows, with the built-in diagonal's kernel instances and the general ones; then two such
+    matrices of different heights in one tree, so that the injection level sees an edge digest."""
+    import plonky3_recursion_amd as p3r
+    if general:
+        rng = np.random.default_rng(15)
+        w32 = (rand(rng, field, oracle_lib.default_w32(field)[0].shape), rand(rng, field, (32,)))
+        c = p3r.Context(field=field, mmcs_arity=4, poseidon2_w32_rc=w32[0], poseidon2_w32_diag=w32[1])
+    else:
+        w32 = None
+        c = p3r.Context(field=field, mmcs_arity=4, allow_unpinned_w32_defaults=True)
+    for h in (1, 64):
+        for w in (1, 23, 24, 25, 48, 49):
+            for k, m in enumerate(edge_matrices(field, h, w)):
+                cap, tree = c.commit([m])
+                ocap, otree = oracle.commit4(field, [m], w32=w32)
+                assert np.array_equal(cap, ocap), (h, w, k)
+                opened, proof = tree.open_batch(h - 1)
+                oo, op = otree.open(h - 1)
+                assert np.array_equal(opened, oo) and np.array_equal(proof, op), (h, w, k)
+                tree.free()
+    for ka, a in enumerate(edge_matrices(field, 64, 25)):
+        for kb, b in enumerate(edge_matrices(field, 1, 23)):
+            cap, tree = c.commit([a, b])
+            ocap, otree = oracle.commit4(field, [a, b], w32=w32)
+            assert np.array_equal(cap, ocap), (ka, kb)
+            opened, proof = tree.open_batch(33)
+            oo, op = otree.open(33)
+            assert np.array_equal(opened, oo) and np.array_equal(proof, op), (ka, kb)
+            tree.free()
+    c.close()
+
+
 def test_reference_round_trip_pattern_on_the_device(oracle):
     """circuit-prover/tests/arity4_mmcs.rs: a 64 x 4 matrix (three quaternary levels, three siblings a level), indices
     0, 1, 2, 3, 27, 63; the openings must be the ones the W32 TABLE's rows then consume - checked here by feeding the

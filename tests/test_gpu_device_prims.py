@@ -25,5 +25,6 @@ def test_device_primitives_against_numpy():
 def test_product_library_does_not_export_the_seam():
     import ctypes
     lib = ctypes.CDLL(os.path.join(ROOT, "plonky3_recursion_amd", "libp3r_hip.so"))
-    for name in ("p3r_test_exclusive_sum_u32", "p3r_test_exclusive_sum_u64", "p3r_test_reduce_max", "p3r_test_sort_pairs"):
+    for name in ("p3r_test_exclusive_sum_u32", "p3r_test_exclusive_sum_u64", "p3r_test_reduce_max", "p3r_test_sort_pairs",
+                 "p3r_test_p2f_permute", "p3r_test_p2f_store"):
         assert not hasattr(lib, name), name

@@ -178,6 +178,41 @@ def test_mmcs_tall_mixed_heights(oracle, cap_height, ctx):
     c.close()
 
 
+def edge_matrices(field, h, w):
+    """Constant and patterned matrices of the words where a load or a reduction can go wrong: all-zero, all P - 1,
+    alternating 0 / P - 1 by column and by row."""
+    top = P[field] - 1
+    by_col, by_row = np.zeros((h, w), dtype=np.uint32), np.zeros((h, w), dtype=np.uint32)
+    by_col[:, 1::2] = top
+    by_row[1::2, :] = top
+    return [np.zeros((h, w), dtype=np.uint32), np.full((h, w), top, dtype=np.uint32), by_col, by_row]
+
+
+def test_mmcs_edge_words(oracle, ctx):
+    """p2f_load and the sponge's `rem` branches on edge words: widths around the rate (8) and twice the rate, one row and
+    one wavefront of rows; then two such matrices of different heights in one tree, so that the injection level sees an
+    edge digest."""
+    for h in (1, 64):
+        for w in (1, 7, 8, 9, 16, 17):
+            for k, m in enumerate(edge_matrices(ctx.field, h, w)):
+                cap, tree = ctx.commit([m])
+                ocap, otree = oracle.commit(ctx.field, [m], 0)
+                assert np.array_equal(cap, ocap), (h, w, k)
+                opened, proof = tree.open_batch(h - 1)
+                oo, op = otree.open(h - 1)
+                assert np.array_equal(opened, oo) and np.array_equal(proof, op), (h, w, k)
+                tree.free()
+    for ka, a in enumerate(edge_matrices(ctx.field, 64, 9)):
+        for kb, b in enumerate(edge_matrices(ctx.field, 1, 7)):
+            cap, tree = ctx.commit([a, b])
+            ocap, otree = oracle.commit(ctx.field, [a, b], 0)
+            assert np.array_equal(cap, ocap), (ka, kb)
+            opened, proof = tree.open_batch(33)
+            oo, op = otree.open(33)
+            assert np.array_equal(opened, oo) and np.array_equal(proof, op), (ka, kb)
+            tree.free()
+
+
 def test_mmcs_golden_sponge(ctx, golden):
     g = golden["prim"][key_of(ctx)]
     for kat in g["sponge"]:
