@@ -15,6 +15,7 @@
  *     -> Poseidon2CircuitAir::generate_trace_rows       poseidon2-circuit-air/src/air.rs:280-520
  *   Mmcs::commit / open_batch (MerkleTreeMmcs)          circuit-prover/src/config.rs:56-63,129
  *   TwoAdicSubgroupDft::coset_lde_batch                 circuit-prover/src/config.rs:55,131
+ *   TwoAdicSubgroupDft::dft_batch / idft_batch / coset_dft_batch / coset_idft_batch   (the same Dft; p3r_dft*)
  *   CryptographicPermutation<[F;16]>::permute           circuit-prover/src/config.rs:126-136
  *
  * Conventions (mirroring the reference's Result<_, String> stringification at
@@ -278,6 +279,36 @@ int p3r_coset_lde(p3r_ctx* ctx, const uint32_t* evals, size_t h, size_t w, uint3
                   uint32_t shift, uint32_t* out);
 p3r_dmat* p3r_coset_lde_dmat(p3r_ctx* ctx, const p3r_dmat* evals, uint32_t added_bits,
                              uint32_t shift);
+
+/* The two halves of the LDE on their own: the `Dft` of a configuration (the Radix2DitParallel<F> of
+ * circuit-prover/src/config.rs:55,131), i.e. p3_dft::TwoAdicSubgroupDft.  Every column of an h x w matrix is one
+ * polynomial of degree < h.  The COEFFICIENT side is always in natural order (row k = coefficient of x^k);
+ * eval_order describes the EVALUATION side in both directions - the output of a P3R_DFT_FORWARD call, the input of
+ * a P3R_DFT_INVERSE call.
+ *   TwoAdicSubgroupDft::dft_batch          P3R_DFT_FORWARD, shift 1, P3R_DFT_NATURAL   (the one required method)
+ *   TwoAdicSubgroupDft::idft_batch         P3R_DFT_INVERSE, shift 1, P3R_DFT_NATURAL
+ *   TwoAdicSubgroupDft::coset_dft_batch    P3R_DFT_FORWARD, any other non-zero canonical shift
+ *   TwoAdicSubgroupDft::coset_idft_batch   P3R_DFT_INVERSE, any other non-zero canonical shift
+ *   P3R_DFT_BITREV                         the same followed (forward) / preceded (inverse) by
+ *                                          BitReversibleMatrix::bit_reverse_rows, without a pass of its own over a
+ *                                          forward result (the passes produce that order)
+ *   TwoAdicSubgroupDft::dft_algebra_batch  needs no entry: an h x w matrix of D-word extension elements IS the
+ *                                          h x (w * D) base matrix (the transform is linear over the base field)
+ * Inputs are never modified; outs[i] is a fresh matrix the caller frees.  Heights are powers of two from 1 to
+ * 2^TWO_ADICITY (24 KoalaBear, 27 BabyBear), widths >= 1 (2^27 rows, BabyBear only, is P3R_EUNSUPPORTED here as in
+ * p3r_coset_lde: its 2^14-row NTT tile does not fit the LDS).  P3R_EINVAL, before anything is allocated or launched: a
+ * height that is not a power of two or is above the two-adicity, shift 0 or >= p, an unknown direction or order,
+ * n_mats == 0, a non-canonical host word.  All matrices of a batch go through the device together (one launch per
+ * pass), whatever their heights. */
+#define P3R_DFT_FORWARD 0   /* coefficients -> evaluations */
+#define P3R_DFT_INVERSE 1   /* evaluations -> coefficients */
+#define P3R_DFT_NATURAL 0   /* evaluation row i is the point shift * w_h^i */
+#define P3R_DFT_BITREV  1   /* evaluation row i is the point shift * w_h^bitrev(i) */
+int p3r_dft(p3r_ctx* ctx, const uint32_t* rowmajor_in, size_t h, size_t w, uint32_t direction, uint32_t shift,
+            uint32_t eval_order, uint32_t* rowmajor_out);
+int p3r_dft_batch_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats, uint32_t direction,
+                       const uint32_t* shifts /* n_mats, canonical */, uint32_t eval_order,
+                       p3r_dmat** outs /* n_mats, caller frees */);
 
 /* ---- K6: MMCS (MerkleTreeMmcs<PaddingFreeSponge<Perm,16,8,8>, TruncatedPermutation<Perm,2,8,16>>) ---- */
 

@@ -114,6 +114,49 @@ class Context {
   p3r_ctx* h_ = nullptr;
 };
 
+// The `Dft` of a configuration over device matrices: p3_dft::TwoAdicSubgroupDft (the Radix2DitParallel<F> of
+// circuit-prover/src/config.rs:55,131).  Matrices are p3r_dmat handles (p3r_dmat_upload / p3r_dmat_free); inputs are
+// left as they are, every result is a fresh handle the caller frees.  Coefficients are in natural order;
+// `bit_reversed` describes the evaluation side (p3r.h: P3R_DFT_BITREV).  dft_algebra_batch needs no method: an h x w
+// matrix of D-word extension elements is the h x (w * D) base matrix.
+class Dft {
+ public:
+  explicit Dft(const Context& ctx) : ctx_(&ctx) {}
+  using Mats = std::vector<const p3r_dmat*>;
+  std::vector<p3r_dmat*> dft_batch(const Mats& mats, bool bit_reversed = false) const {
+    return run(mats, P3R_DFT_FORWARD, std::vector<uint32_t>(mats.size(), 1u), bit_reversed);
+  }
+  std::vector<p3r_dmat*> idft_batch(const Mats& mats, bool bit_reversed = false) const {
+    return run(mats, P3R_DFT_INVERSE, std::vector<uint32_t>(mats.size(), 1u), bit_reversed);
+  }
+  std::vector<p3r_dmat*> coset_dft_batch(const Mats& mats, uint32_t shift, bool bit_reversed = false) const {
+    return run(mats, P3R_DFT_FORWARD, std::vector<uint32_t>(mats.size(), shift), bit_reversed);
+  }
+  std::vector<p3r_dmat*> coset_idft_batch(const Mats& mats, uint32_t shift, bool bit_reversed = false) const {
+    return run(mats, P3R_DFT_INVERSE, std::vector<uint32_t>(mats.size(), shift), bit_reversed);
+  }
+  // rows in bit-reversed order, as TwoAdicFriPcs::commit keeps them (p3r_coset_lde_dmat)
+  std::vector<p3r_dmat*> coset_lde_batch(const Mats& mats, uint32_t added_bits, uint32_t shift) const {
+    std::vector<p3r_dmat*> outs;
+    try {
+      for (const p3r_dmat* m : mats) outs.push_back(ctx_->ptr(p3r_coset_lde_dmat(ctx_->raw(), m, added_bits, shift)));
+    } catch (...) {
+      for (p3r_dmat* o : outs) p3r_dmat_free(ctx_->raw(), o);
+      throw;
+    }
+    return outs;
+  }
+
+ private:
+  std::vector<p3r_dmat*> run(const Mats& mats, uint32_t direction, const std::vector<uint32_t>& shifts, bool bit_reversed) const {
+    std::vector<p3r_dmat*> outs(mats.size(), nullptr);
+    ctx_->check(p3r_dft_batch_dmat(ctx_->raw(), mats.data(), mats.size(), direction, shifts.data(),
+                                   bit_reversed ? P3R_DFT_BITREV : P3R_DFT_NATURAL, outs.data()));
+    return outs;
+  }
+  const Context* ctx_;
+};
+
 struct TablePacking {
   uint32_t public_lanes = 1, alu_lanes = 3, horner_packed_steps = 4, recompose_lanes = 1, min_trace_height = 1;
   static TablePacking create(uint32_t public_lanes, uint32_t alu_lanes) {  // TablePacking::new

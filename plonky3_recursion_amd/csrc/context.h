@@ -575,6 +575,8 @@ struct p3r_ctx {
   std::map<std::pair<int, int>, p3r::DevBuf> tw_sub;                 // (log_r, inverse)
   std::map<std::pair<int, int>, std::pair<p3r::DevBuf, p3r::DevBuf>> tw4;  // (log_n, inverse) -> (lo, hi)
   std::map<std::tuple<int, int, uint32_t>, std::pair<p3r::DevBuf, p3r::DevBuf>> pre;  // (log_n, added_bits, shift)
+  // coefficient scaling of the coset inverse transforms (tu_lde.hip::get_inv_pow); apart from `pre`, which the LDE reads
+  std::map<std::pair<int, uint32_t>, std::pair<p3r::DevBuf, p3r::DevBuf>> inv_pow;  // (log_n, shift)
 };
 
 // `words` cells from device memory into `dst` (host), for results the host transcript waits on.

@@ -40,6 +40,11 @@ struct NttPass {
   // starting at block0; 2^log_gx tiles per polynomial and coset, 2^log_gz cosets
   uint32_t block0;
   int log_gx, log_gz;
+  // optional per-coefficient output scaling of the LAST inverse pass (coset inverse transform): cell o of the output
+  // column is multiplied by post_a[o >> post_log] * post_b[o & (2^post_log - 1)] = shift^-o / N
+  const uint32_t* post_a;
+  const uint32_t* post_b;
+  int post_log;
 };
 
 constexpr int kNttBlock = 512;  // launches use tile_cells/16 lanes (2^13-cell tiles)
@@ -62,6 +67,8 @@ struct NttTileIo {
   gptr<const uint32_t> tw4_hi;
   uint32_t line0, N1, N2;
   int log_r;
+  gptr<const uint32_t> post_a;
+  gptr<const uint32_t> post_b;
   __device__ __forceinline__ F load(uint32_t r, uint32_t t) const {
     uint32_t n1, n2;
     if (a.sub_dim == 0) { n1 = r; n2 = line0 + t; } else { n1 = line0 + t; n2 = r; }
@@ -82,6 +89,7 @@ struct NttTileIo {
     size_t o;
     if (a.sub_dim == 0) o = a.out_mode == 2 ? (size_t)line * N1 + rho : (size_t)rho * N2 + line;
     else o = (size_t)line * N2 + rho;
+    if (post_a) v = v * (F::raw(post_a[o >> a.post_log]) * F::raw(post_b[o & ((size_t(1) << a.post_log) - 1)]));
     out[o] = v.v;
   }
 };
@@ -180,7 +188,8 @@ __global__ void __launch_bounds__(kNttBlock, 8) k_ntt_tile(const NttPass* __rest
                    a.pre_a ? as_global(a.pre_a) + (size_t)bz * N1 : nullptr,
                    a.pre_b ? as_global(a.pre_b) + (size_t)bz * N2 : nullptr,
                    as_global(a.tw4_lo), as_global(a.tw4_hi),
-                   bx * T, N1, N2, log_r};
+                   bx * T, N1, N2, log_r,
+                   as_global(a.post_a), as_global(a.post_b)};
   const gptr<const uint32_t> tw_sub = as_global(a.tw_sub);
   for (uint32_t i = tid; i < R / 2; i += blockDim.x) tws[i] = tw_sub[i];
   __syncthreads();

@@ -222,15 +222,17 @@ __global__ void __launch_bounds__(256) k_ntt_fwd_line_mixed(const NttLineJob* __
 //   NTT2_INV1  inverse pass 1: output times w_N^-(k1*n2), stored TRANSPOSED in natural order,
 //              out[n2*N1 + k1] (through LDS, so that lanes run along k1)
 //   NTT2_INV2  inverse pass 2: output times `scale` (1/N), natural order, out[k1*N2 + n2]
-enum { NTT2_FWD = 0, NTT2_INV1 = 1, NTT2_INV2 = 2 };
+//   NTT2_INV2C inverse pass 2 of a COSET inverse transform: as NTT2_INV2, but output cell k1*N2 + n2 is coefficient
+//              k1*N2 + n2 times shift^-(k1*N2 + n2) / N = pre_a[k1] * pre_b[n2] (pre_a carries the 1/N)
+enum { NTT2_FWD = 0, NTT2_INV1 = 1, NTT2_INV2 = 2, NTT2_INV2C = 3 };
 struct NttColJob {
   const uint32_t* in;
   uint32_t* out;
   const uint32_t* tw;      // w_R^(+-i), i < R/2
   const uint32_t* tw4_lo;  // w_N^(+-x) = hi[x >> 10] * lo[x & 1023]
   const uint32_t* tw4_hi;
-  const uint32_t* pre_a;   // [cosets][N1]: s_z^(N2*n1)
-  const uint32_t* pre_b;   // [cosets][N2]: s_z^n2
+  const uint32_t* pre_a;   // [cosets][N1]: s_z^(N2*n1)          (NTT2_INV2C: [N1] shift^-(N2*k1) / N)
+  const uint32_t* pre_b;   // [cosets][N2]: s_z^n2               (NTT2_INV2C: [N2] shift^-n2)
   uint64_t in_col_stride, out_col_stride, out_coset_stride;
   int log_n2, log_cosets;
   int log_r;        // sub-transform size (read by the mixed-size launch only)
@@ -372,6 +374,15 @@ __device__ __forceinline__ void ntt2_col_body(const NttColJob& a, uint32_t local
         const uint32_t k1 = bit_reverse(r0 + j, LOG_R);
         dst[((size_t)k1 << a.log_n2) + n2] = (x[j] * sc).v;
       }
+    } else if constexpr (MODE == NTT2_INV2C) {
+      // natural row order, coefficient k1*N2 + n2 times shift^-(k1*N2 + n2) / N: the column part is the lane's own
+      const gptr<const uint32_t> pa = as_global(a.pre_a);
+      const F pb = F::raw(as_global(a.pre_b)[n2]);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const uint32_t k1 = bit_reverse(r0 + j, LOG_R);
+        dst[((size_t)k1 << a.log_n2) + n2] = (x[j] * (F::raw(pa[k1]) * pb)).v;
+      }
     } else {
       // transposed: back through LDS so that consecutive lanes write consecutive k1
 #pragma unroll
@@ -421,6 +432,58 @@ __global__ void __launch_bounds__(kNtt2Lanes) k_ntt_col_mixed(const NttColJob* _
     case 10: ntt2_col_body<PP, 10, MODE, 13>(a, local, tile, tws); break;
     case 11: ntt2_col_body<PP, 11, MODE, 13>(a, local, tile, tws); break;
     default: ntt2_col_body<PP, 12, MODE, 13>(a, local, tile, tws); break;
+  }
+}
+
+// ------------------------------------------------------------------ row bit-reversal of column-major matrices
+// out[col][bitrev(i)] = in[col][i] for columns of N = 2^log_n cells (the evaluation side of a transform in natural
+// order: the forward passes leave bit-reversed rows).  With t = log_t, i = H * 2^(n-t) + M * 2^t + L (H, L of t bits)
+// goes to bitrev(L) * 2^(n-t) + bitrev(M) * 2^t + bitrev(H): a workgroup takes the 2^t x 2^t cells of one M - 2^t
+// segments of 2^t consecutive cells on the way in, the same on the way out - through an LDS tile that swaps the roles
+// of H and L.  t = 6: every wave access is one 256-byte segment; t = 5 (2^10 and 2^11 rows): two 128-byte segments.
+// In the store phase lane u holds H = u and writes cell bitrev(u) of its segment: the LDS reads tile[u][L] run down
+// a column of the padded tile (row pitch 2^t + 1: conflict-free, like the row-wise writes), and the wave still
+// writes one whole segment - the lanes are merely permuted inside it.
+// log_t = 0: columns shorter than 2^10 cells, one workgroup per column, cell by cell (a column is at most 2 KiB).
+struct BitrevJob {
+  const uint32_t* in;
+  uint32_t* out;      // never the same matrix as `in`
+  uint32_t log_n;
+  uint32_t log_t;     // 6, 5 or 0 (see above)
+  uint32_t block0;    // a job owns columns << (log_n - 2*log_t) blocks (log_t = 0: one per column)
+};
+constexpr int kBitrevLanes = 256;
+constexpr int kBitrevMinTiled = 10;  // log_n from which the tiled form is used
+
+template <int LOG_T>
+__device__ __forceinline__ void bitrev_rows_tile(const BitrevJob& a, uint32_t local, uint32_t* tile) {
+  constexpr uint32_t T = 1u << LOG_T, STEP = kBitrevLanes >> LOG_T;
+  const int log_m = (int)a.log_n - 2 * LOG_T, log_seg = (int)a.log_n - LOG_T;
+  const uint32_t m = local & ((1u << log_m) - 1), col = local >> log_m;
+  const gptr<const uint32_t> src = as_global(a.in) + ((size_t)col << a.log_n) + ((size_t)m << LOG_T);
+  const gptr<uint32_t> dst = as_global(a.out) + ((size_t)col << a.log_n) + ((size_t)bit_reverse(m, log_m) << LOG_T);
+  const uint32_t u = threadIdx.x & (T - 1), v0 = threadIdx.x >> LOG_T;
+#pragma unroll 4
+  for (uint32_t H = v0; H < T; H += STEP) tile[H * (T + 1) + u] = src[((size_t)H << log_seg) + u];
+  __syncthreads();
+  const uint32_t ru = bit_reverse(u, LOG_T);
+#pragma unroll 4
+  for (uint32_t L = v0; L < T; L += STEP) dst[((size_t)bit_reverse(L, LOG_T) << log_seg) + ru] = tile[u * (T + 1) + L];
+}
+
+__global__ void __launch_bounds__(kBitrevLanes) k_bitrev_rows(const BitrevJob* __restrict__ jobs, int n_jobs) {
+  __shared__ uint32_t tile[64 * 65];
+  const int jb = find_job(jobs, n_jobs);
+  const BitrevJob& a = jobs[jb];
+  const uint32_t local = blockIdx.x - a.block0;
+  if (a.log_t == 6) {
+    bitrev_rows_tile<6>(a, local, tile);
+  } else if (a.log_t == 5) {
+    bitrev_rows_tile<5>(a, local, tile);
+  } else {
+    const gptr<const uint32_t> src = as_global(a.in) + ((size_t)local << a.log_n);
+    const gptr<uint32_t> dst = as_global(a.out) + ((size_t)local << a.log_n);
+    for (uint32_t i = threadIdx.x; i < (1u << a.log_n); i += kBitrevLanes) dst[bit_reverse(i, (int)a.log_n)] = src[i];
   }
 }
 

@@ -559,6 +559,40 @@ int p3r_coset_lde(p3r_ctx* ctx, const uint32_t* evals, size_t h, size_t w, uint3
   });
 }
 
+// TwoAdicSubgroupDft::dft_batch / idft_batch / coset_dft_batch / coset_idft_batch: one half of the LDE (tu_lde.hip)
+static void dft_check_modes(uint32_t direction, uint32_t eval_order) {
+  if (direction != P3R_DFT_FORWARD && direction != P3R_DFT_INVERSE) fail(P3R_EINVAL, "unknown DFT direction %u", direction);
+  if (eval_order != P3R_DFT_NATURAL && eval_order != P3R_DFT_BITREV) fail(P3R_EINVAL, "unknown DFT evaluation order %u", eval_order);
+}
+int p3r_dft_batch_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats, uint32_t direction, const uint32_t* shifts,
+                       uint32_t eval_order, p3r_dmat** outs) {
+  return guard(ctx, [&] {
+    if (!mats || !shifts || !outs || n_mats == 0) fail(P3R_EINVAL, "bad arguments");
+    dft_check_modes(direction, eval_order);
+    std::vector<LdeItem> items(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
+      items[i] = {mats[i], shifts[i]};
+    }
+    auto res = P3R_FIELD_CALL(ctx, dft_batch, ctx, items, direction == P3R_DFT_INVERSE, eval_order == P3R_DFT_BITREV);
+    for (size_t i = 0; i < n_mats; ++i) outs[i] = res[i].release();
+  });
+}
+int p3r_dft(p3r_ctx* ctx, const uint32_t* rowmajor_in, size_t h, size_t w, uint32_t direction, uint32_t shift,
+            uint32_t eval_order, uint32_t* rowmajor_out) {
+  return guard(ctx, [&] {
+    if (!rowmajor_in || !rowmajor_out) fail(P3R_EINVAL, "NULL argument");
+    dft_check_modes(direction, eval_order);
+    P3R_FIELD_CALL(ctx, dft_check, h, w, shift);
+    const uint32_t p = ctx->cfg.field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
+    for (size_t i = 0; i < h * w; ++i)
+      if (rowmajor_in[i] >= p) fail(P3R_EINVAL, "non-canonical field element at word %zu", i);
+    auto in = P3R_FIELD_CALL(ctx, upload, ctx, rowmajor_in, h, w);
+    auto res = P3R_FIELD_CALL(ctx, dft_batch, ctx, {{in.get(), shift}}, direction == P3R_DFT_INVERSE, eval_order == P3R_DFT_BITREV);
+    P3R_FIELD_CALL(ctx, download, ctx, res[0].get(), rowmajor_out);
+  });
+}
+
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,
                          uint32_t* cap_out, p3r_tree** tree_out) {
   return guard(ctx, [&] {

@@ -46,6 +46,20 @@ struct LdeItem {
 };
 template <class PP>
 std::vector<std::unique_ptr<p3r_dmat>> coset_lde_batch(p3r_ctx* ctx, const std::vector<LdeItem>& items, int added_bits);
+// The halves of the LDE on their own (tu_lde.hip): TwoAdicSubgroupDft::dft_batch / idft_batch (shift 1) and
+// coset_dft_batch / coset_idft_batch.  Every column of an h x w matrix is a polynomial of degree < h; the coefficient
+// side is in natural order, `bit_reversed` says whether evaluation row i is the point shift * w_h^bitrev(i) or
+// shift * w_h^i - the output of a forward call, the input of an inverse one.  Inputs are read only.
+// dft_check: what both refuse, before anything is allocated or launched.
+template <class PP>
+inline void dft_check(size_t h, size_t w, uint32_t shift) {
+  const int log_n = log2_exact(h, "DFT height");
+  if (log_n > PP::TWO_ADICITY) fail(P3R_EINVAL, "DFT of 2^%d rows exceeds the field's two-adicity (%d)", log_n, PP::TWO_ADICITY);
+  if (w == 0) fail(P3R_EINVAL, "matrix width must be positive");
+  if (shift == 0 || shift >= PP::P) fail(P3R_EINVAL, "coset shift must be a non-zero canonical element");
+}
+template <class PP>
+std::vector<std::unique_ptr<p3r_dmat>> dft_batch(p3r_ctx* ctx, const std::vector<LdeItem>& items, bool inverse, bool bit_reversed);
 // once per context: kernel attributes of the unit's kernels
 template <class PP>
 void lde_init(p3r_ctx* ctx);

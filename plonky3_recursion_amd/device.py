@@ -5,6 +5,7 @@ Names follow the reference's traits where one exists:
                         recursion/examples/common/mod.rs:464-486 (FRI params + Poseidon2 perms)
   MerkleTree.commit/open_batch   p3_commit::Mmcs::{commit, open_batch}
   coset_lde_batch       p3_dft::TwoAdicSubgroupDft::coset_lde_batch (+ bit_reverse_rows)
+  dft_batch             p3_dft::TwoAdicSubgroupDft::{dft_batch, idft_batch, coset_dft_batch, coset_idft_batch}
   permute_batch         CryptographicPermutation<[F;16]>::permute over a batch
   generate_trace_rows   Poseidon2CircuitAir::generate_trace_rows (poseidon2-circuit-air/src/air.rs:280)
 """
@@ -321,6 +322,45 @@ class Context:
 
     def coset_lde_batch_device(self, dmat, added_bits, shift):
         return DeviceMatrix(self, self.ptr(self.lib.p3r_coset_lde_dmat(self.h, dmat.h, added_bits, shift)))
+
+    # ---- DFT: the two halves of the LDE on their own
+    def dft_batch(self, mats, inverse=False, shifts=None, bit_reversed=False):
+        """TwoAdicSubgroupDft::dft_batch (`inverse`: idft_batch; `shifts`: coset_dft_batch / coset_idft_batch, one
+        canonical shift per matrix or one for all) over host matrices (2-D uint32 arrays, one polynomial per column,
+        canonical words).  Coefficients are in natural order; `bit_reversed` says whether evaluation row i is the point
+        shift * w^bitrev(i) instead of shift * w^i - the output of a forward call, the input of an inverse one.
+        Returns the list of transformed matrices."""
+        outs = []
+        for m, s in zip(mats, self._dft_shifts(shifts, len(mats))):
+            a, p = _u32(m)
+            assert a.ndim == 2
+            out = np.empty(a.shape, dtype=np.uint32)
+            self.check(self.lib.p3r_dft(self.h, p, a.shape[0], a.shape[1], _lib.P3R_DFT_INVERSE if inverse else _lib.P3R_DFT_FORWARD,
+                                        s, _lib.P3R_DFT_BITREV if bit_reversed else _lib.P3R_DFT_NATURAL,
+                                        out.ctypes.data_as(_lib.u32p)))
+            outs.append(out)
+        return outs
+
+    def dft_batch_device(self, dmats, inverse=False, shifts=None, bit_reversed=False):
+        """The same over DeviceMatrix handles, all matrices in one call (one launch per pass whatever their heights);
+        the inputs are left as they are, the results are new DeviceMatrix objects."""
+        n = len(dmats)
+        arr = (C.c_void_p * n)(*[d.h for d in dmats])
+        sh, sp = _u32(self._dft_shifts(shifts, n))
+        outs = (C.c_void_p * n)()
+        self.check(self.lib.p3r_dft_batch_dmat(self.h, arr, n, _lib.P3R_DFT_INVERSE if inverse else _lib.P3R_DFT_FORWARD, sp,
+                                               _lib.P3R_DFT_BITREV if bit_reversed else _lib.P3R_DFT_NATURAL, outs))
+        return [DeviceMatrix(self, self.ptr(h)) for h in outs]
+
+    @staticmethod
+    def _dft_shifts(shifts, n):
+        if shifts is None:
+            return [1] * n
+        if np.ndim(shifts) == 0:
+            return [int(shifts)] * n
+        if len(shifts) != n:
+            raise P3rError(-1, "one shift per matrix")
+        return [int(s) for s in shifts]
 
     # ---- MMCS
     def commit(self, mats):
