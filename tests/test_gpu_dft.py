@@ -266,3 +266,156 @@ def test_refusals_are_einval_and_the_context_still_proves(ctxs, oracle, field):
     L.verify(proof)
     assert proof == L.prove()
     pd.free()
+
+
+# ---------------------------------------------------------------- 8. edge words, every cell, by closed forms
+# Columns of the words where a butterfly's range argument is tightest (P - 1 and 0, constant, alternating, a single
+# entry).  Such a column is a geometric sum, so F(z) = sum_j E_j z^j has a closed form that costs O(1) per point given
+# z^h and z^(h/2), and EVERY cell of the transform is checked.  The closed forms are kept free of inverses by clearing
+# the denominator:  den(z) * F(z) == num(z)  determines F(z) wherever den(z) != 0, and where it is zero (z = 1, z = -1)
+# the sum is written out.  KINDS names a column by its entries in natural index order.
+KINDS = ("zero", "const", "odd", "impulse0", "impulse_last", "alt", "upper", "signtop")
+# a row pattern of a bit-reversed evaluation matrix, read in natural point order
+BITREV_KIND = {"zero": "zero", "const": "const", "odd": "upper", "impulse0": "impulse0", "impulse_last": "impulse_last",
+               "alt": "signtop"}
+
+
+def kind_column(kind, h, p):
+    """The column itself (uint64, natural order), c = P - 1."""
+    c, e = p - 1, np.zeros(h, dtype=np.uint64)
+    if kind == "const":
+        e[:] = c
+    elif kind == "odd":
+        e[1::2] = c
+    elif kind == "impulse0":
+        e[0] = c
+    elif kind == "impulse_last":
+        e[h - 1] = c
+    elif kind == "alt":             # c * (-1)^j
+        e[0::2], e[1::2] = c, (p - c) % p
+    elif kind == "upper":
+        e[h // 2:] = c
+    elif kind == "signtop":         # c below h/2, -c from there
+        e[:h // 2], e[h // 2:] = c, (p - c) % p
+    else:
+        assert kind == "zero"
+    return e
+
+
+def closed_form_holds(kind, F, z, zhalf, zh, h, p):
+    """Is F[i] = sum_j E_j z[i]^j for the column `kind`?  z, zhalf = z^(h/2), F: uint64 arrays; zh = z^h, one integer
+    for all points (they lie on one coset)."""
+    P, c, m1 = np.uint64(p), p - 1, p - 1
+    if kind == "zero":
+        return not F.any()
+    if kind == "impulse0":
+        return bool((F == c).all())
+    if kind == "impulse_last":      # z * z^(h-1) = z^h
+        return bool((F * z % P == c * zh % p).all())
+    if kind == "const":             # (z - 1) sum z^j = z^h - 1
+        den, num, at_zero = (z + m1) % P, c * (zh - 1) % p, c * h % p
+    elif kind == "odd":             # sum of z^(2j+1):  (z^2 - 1) F = z (z^h - 1)
+        den, num, at_zero = (z * z % P + m1) % P, c * (zh - 1) % p * z % P, c * (h // 2) % p * z % P
+    elif kind == "alt":             # (-z - 1) sum (-z)^j = (z^h - 1), h even
+        den, num, at_zero = (z + 1) % P, c * (1 - zh) % p, c * h % p
+    elif kind == "upper":           # z^(h/2) sum_{j < h/2} z^j
+        den, num, at_zero = (z + m1) % P, c * zhalf % P * ((zhalf + m1) % P) % P, c * (h // 2) % p
+    else:                           # (1 - z^(h/2)) sum_{j < h/2} z^j
+        assert kind == "signtop"
+        t = (zhalf + m1) % P
+        den, num, at_zero = (z + m1) % P, (p - c) % p * (t * t % P) % P, 0
+    return bool(np.where(den != 0, F * den % P == num, F == at_zero).all())
+
+
+def bitrev_indices(h):
+    bits, idx = h.bit_length() - 1, np.arange(h, dtype=np.uint64)
+    rev = np.zeros(h, dtype=np.uint64)
+    for i in range(bits):
+        rev |= ((idx >> np.uint64(i)) & np.uint64(1)) << np.uint64(bits - 1 - i)
+    return rev.astype(np.int64)
+
+
+def points_forward(field, h, shift, bit_reversed):
+    """z, z^(h/2), z^h of the rows of a forward result: row i is the point shift * w^i (w^bitrev(i))."""
+    p = oracle_lib.MODULUS[field]
+    idx = bitrev_indices(h) if bit_reversed else np.arange(h, dtype=np.int64)
+    z = power_table(omega(field, h), h, p)[idx] * np.uint64(shift) % np.uint64(p)
+    zhalf = np.where(idx & 1, np.uint64(pow(shift, h // 2, p) * (p - 1) % p), np.uint64(pow(shift, h // 2, p)))
+    return z, zhalf, pow(shift, h, p)
+
+
+def points_inverse(field, h, shift):
+    """Coefficient k of an inverse result is  shift^-k / h * F(w^-k),  F over the evaluations in natural point order:
+    the points w^-k, their powers, and the factor h * shift^k that turns the coefficient into F."""
+    p = oracle_lib.MODULUS[field]
+    z = power_table(pow(omega(field, h), p - 2, p), h, p)
+    zhalf = np.where(np.arange(h) & 1, np.uint64(p - 1), np.uint64(1))
+    return z, zhalf, 1, power_table(shift, h, p) * np.uint64(h % p) % np.uint64(p)
+
+
+def assert_closed_forms_are_the_definition(field):
+    """At h = 64: closed_form_holds accepts exactly sum_j E_j z^j as evaluate() computes it, on a coset and on the subgroup
+    (where z = 1 and z = -1 occur), and refuses a cell that is off by one; BITREV_KIND is the bit-reversal of the rows."""
+    p, h = oracle_lib.MODULUS[field], 64
+    rev = bitrev_indices(h)
+    for kind, nat in BITREV_KIND.items():
+        assert np.array_equal(kind_column(kind, h, p)[rev], kind_column(nat, h, p)), kind
+    sets = [points_forward(field, h, s, br) for s in (1, oracle_lib.GENERATOR[field]) for br in (False, True)]
+    sets.append(points_inverse(field, h, 1)[:3])
+    for kind in KINDS:
+        col = kind_column(kind, h, p)[:, None]
+        for z, zhalf, zh in sets:
+            F = np.array([evaluate(col, power_table(int(x), h, p), p)[0] for x in z], dtype=np.uint64)
+            assert closed_form_holds(kind, F, z, zhalf, zh, h, p), (field, kind)
+            for at in (0, 1, h // 2, h - 1):
+                off = F.copy()
+                off[at] = (off[at] + np.uint64(1)) % np.uint64(p)
+                assert not closed_form_holds(kind, off, z, zhalf, zh, h, p), (field, kind, at)
+
+
+def edge_word_matrices(p, h, w):
+    """[(matrix, kind of each column)]: all P - 1; alternating 0 / P - 1 by row; alternating by column; a single P - 1
+    at row 0; at row h - 1; the column (P - 1) * (-1)^i."""
+    out = []
+    for kinds in (["const"] * w, ["odd"] * w, [("const" if c & 1 else "zero") for c in range(w)], ["impulse0"] * w,
+                  ["impulse_last"] * w, ["alt"] * w):
+        out.append((np.stack([kind_column(k, h, p) for k in kinds], axis=1).astype(np.uint32), kinds))
+    return out
+
+
+@pytest.mark.parametrize("field,h,w", cases(LARGE, tall=True))
+def test_edge_words_every_cell_by_closed_forms(ctxs, field, h, w):
+    ctx, p = ctxs(field), oracle_lib.MODULUS[field]
+    assert_closed_forms_are_the_definition(field)
+    mats = edge_word_matrices(p, h, w)
+    dms = [ctx.upload(m) for m, _ in mats]
+
+    def check_columns(out, kinds, holds, what):
+        # equal input columns give equal output columns: the closed form on the first of each kind, equality on the rest
+        first = {}
+        for c, kind in enumerate(kinds):
+            if kind in first:
+                assert np.array_equal(out[:, c], out[:, first[kind]]), what + (c, "differs from column", first[kind])
+            else:
+                first[kind] = c
+                assert holds(kind, out[:, c].astype(np.uint64)), what + (c, kind)
+
+    for shift in (1, oracle_lib.GENERATOR[field]):
+        for bit_reversed in (False, True):
+            z, zhalf, zh = points_forward(field, h, shift, bit_reversed)
+            outs = ctx.dft_batch_device(dms, shifts=shift, bit_reversed=bit_reversed)
+            for (m, kinds), o in zip(mats, outs):
+                check_columns(o.download(), kinds, lambda kind, F: closed_form_holds(kind, F, z, zhalf, zh, h, p),
+                              (shift, bit_reversed, "forward"))
+                o.free()
+            iz, izhalf, izh, scale = points_inverse(field, h, shift)
+            outs = ctx.dft_batch_device(dms, inverse=True, shifts=shift, bit_reversed=bit_reversed)
+            for (m, kinds), o in zip(mats, outs):
+                nat = [BITREV_KIND[k] for k in kinds] if bit_reversed else kinds
+                check_columns(o.download(), nat,
+                              lambda kind, c: closed_form_holds(kind, c * scale % np.uint64(p), iz, izhalf, izh, h, p),
+                              (shift, bit_reversed, "inverse"))
+                o.free()
+    for dm, (m, _) in zip(dms, mats):
+        assert np.array_equal(dm.download(), m), "the input matrix was modified"
+        dm.free()

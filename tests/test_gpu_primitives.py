@@ -241,3 +241,12 @@ def test_commit_device_resident_pipeline(ctx, oracle):
     oo, op = otree.open(1234)
     assert np.array_equal(opened, oo) and np.array_equal(proof, op)
     tree.free()
+
+
+@pytest.mark.parametrize("log_h,w,added", [(11, 3, 2), (12, 3, 2), (13, 2, 1), (16, 2, 2)])
+def test_lde_edge_words(ctx, oracle, log_h, w, added):
+    """The NTT butterflies on edge words, one size per path (single tile, generic two-pass, first lean size, forward split
+    capped at 2^8): all-zero, all P - 1, alternating 0 / P - 1 by column and by row."""
+    shift = oracle_lib.GENERATOR[ctx.field]
+    for k, m in enumerate(edge_matrices(ctx.field, 1 << log_h, w)):
+        assert np.array_equal(ctx.coset_lde_batch(m, added, shift), oracle.coset_lde(ctx.field, m, added, shift)), k
