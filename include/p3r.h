@@ -373,6 +373,41 @@ size_t p3r_tree_log_max_height(const p3r_tree* tree);
 size_t p3r_tree_total_width(const p3r_tree* tree);
 void p3r_tree_free(p3r_ctx* ctx, p3r_tree* tree);
 
+/* ---- the value half of Pcs::open ----
+ *
+ * TwoAdicFriPcs::open (p3_fri::TwoAdicFriPcs as the `Pcs` of circuit-prover/src/config.rs) has two halves: it evaluates
+ * every committed matrix at its opening points (p3_interpolation::interpolate_coset on the low coset of the
+ * bit-reversed LDE), then runs FRI over the reduced openings.  These entries are the first half alone: no transcript,
+ * no randomness, no proof bytes.  With p3r_coset_lde_dmat + p3r_mmcs_commit_dmat (= Pcs::commit) a caller holds the
+ * committed LDEs on the device and gets the `OpenedValues` of Pcs::open from them without downloading a trace.
+ *
+ * p3r_open_points_dmat  == the `mats_and_points` loop of Pcs::open: for matrix i of height H_i let h_i = H_i >>
+ *                          added_bits.  The evaluations of the interpolant are rows 0 .. h_i (eval_order P3R_DFT_BITREV:
+ *                          the first h_i rows of a bit-reversed LDE of blow-up 2^added_bits, which is how upstream's
+ *                          open reads them) or rows k << added_bits (P3R_DFT_NATURAL).  They are taken as the values over
+ *                          shift * <w_{h_i}>, in that order, of the unique polynomials of degree < h_i, one per column;
+ *                          shift 0 = the field's generator (the shift of Pcs::commit), added_bits 0 = the whole matrix.
+ *                          `points`: canonical words, DC per point (DC = the context's challenge degree, 4 or 5); points
+ *                          point_offsets[i] .. point_offsets[i + 1] belong to matrix i.  values_out (HOST memory):
+ *                          [matrix][point][column][DC] canonical words, i.e. OpenedValues with the rounds flattened.
+ *                          Any number of points per matrix; a matrix element is read once for every
+ *                          P3R_OPEN_POINTS_PER_PASS of them, and all matrices of a call share one weights launch, one
+ *                          dot launch, one reduce launch and one wait.  A matrix of width 0 or without points is legal
+ *                          and contributes nothing.
+ * p3r_open_points       == the same over host matrices (row-major canonical), as p3r_dft stands next to
+ *                          p3r_dft_batch_dmat.
+ * P3R_EINVAL, with a message, before anything is launched: a height that is not a power of two, is smaller than
+ * 2^added_bits or leaves more than 2^TWO_ADICITY evaluations; point_offsets that decrease; a non-canonical point word or
+ * shift; an unknown order; a point that lies IN the evaluation coset (z^h == shift^h) - interpolate_coset divides by
+ * zero there, so the call is refused and no wrong value is returned. */
+#define P3R_OPEN_POINTS_PER_PASS 4 /* points that share one read of a matrix (the accumulators' registers) */
+int p3r_open_points_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats, uint32_t added_bits, uint32_t shift,
+                         uint32_t eval_order, const size_t* point_offsets /* n_mats + 1 */, const uint32_t* points,
+                         uint32_t* values_out);
+int p3r_open_points(p3r_ctx* ctx, const p3r_matrix* mats, size_t n_mats, uint32_t added_bits, uint32_t shift,
+                    uint32_t eval_order, const size_t* point_offsets /* n_mats + 1 */, const uint32_t* points,
+                    uint32_t* values_out);
+
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *
  * p3r_prep_create  == ProverData::from_airs_and_degrees + CircuitProverData::new as called by

@@ -157,6 +157,46 @@ class Dft {
   const Context* ctx_;
 };
 
+// The value half of TwoAdicFriPcs::open over device matrices (p3r.h: p3r_open_points_dmat): what
+// p3_interpolation::interpolate_coset gives for every committed matrix at its opening points, read from the low coset of
+// the bit-reversed LDEs a caller committed (Dft::coset_lde_batch + p3r_mmcs_commit_dmat).  No transcript and no FRI here.
+class CosetInterpolation {
+ public:
+  explicit CosetInterpolation(const Context& ctx) : ctx_(&ctx) {}
+  using Mats = std::vector<const p3r_dmat*>;
+  using Points = std::vector<std::vector<uint32_t>>;   // per matrix: k_i points of DC canonical words each
+  // values[i] = [point][column][DC] canonical words of matrix i; shift 0 = the field's generator
+  std::vector<std::vector<uint32_t>> open_points(const Mats& mats, const Points& points, uint32_t added_bits, uint32_t shift = 0,
+                                                 bool bit_reversed = true) const {
+    const size_t dc = ctx_->config().challenge_degree ? ctx_->config().challenge_degree : 4;
+    if (points.size() != mats.size()) throw Error(P3R_EINVAL, "one list of points per matrix");
+    std::vector<size_t> offs(mats.size() + 1, 0), widths(mats.size(), 0);
+    std::vector<uint32_t> flat;
+    size_t words = 0;
+    for (size_t i = 0; i < mats.size(); ++i) {
+      if (!mats[i] || points[i].size() % dc) throw Error(P3R_EINVAL, "a NULL matrix, or a point that is not DC words");
+      widths[i] = p3r_dmat_width(mats[i]);
+      offs[i + 1] = offs[i] + points[i].size() / dc;
+      flat.insert(flat.end(), points[i].begin(), points[i].end());
+      words += points[i].size() * widths[i];
+    }
+    std::vector<uint32_t> out(words);
+    ctx_->check(p3r_open_points_dmat(ctx_->raw(), mats.data(), mats.size(), added_bits, shift,
+                                     bit_reversed ? P3R_DFT_BITREV : P3R_DFT_NATURAL, offs.data(), flat.data(), out.data()));
+    std::vector<std::vector<uint32_t>> res(mats.size());
+    size_t at = 0;
+    for (size_t i = 0; i < mats.size(); ++i) {
+      const size_t n = points[i].size() * widths[i];
+      res[i].assign(out.begin() + at, out.begin() + at + n);
+      at += n;
+    }
+    return res;
+  }
+
+ private:
+  const Context* ctx_;
+};
+
 struct TablePacking {
   uint32_t public_lanes = 1, alu_lanes = 3, horner_packed_steps = 4, recompose_lanes = 1, min_trace_height = 1;
   static TablePacking create(uint32_t public_lanes, uint32_t alu_lanes) {  // TablePacking::new

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("P3R_LIB_PATH") or os.path.join(_HERE, "libp3r_hip.so"
 P3R_ABI_VERSION = 8
 P3R_DFT_FORWARD, P3R_DFT_INVERSE = 0, 1   # p3r_dft direction
 P3R_DFT_NATURAL, P3R_DFT_BITREV = 0, 1    # p3r_dft eval_order
+P3R_OPEN_POINTS_PER_PASS = 4              # p3r_open_points: points that share one read of a matrix
 P3R_EXT_LOOKUP_UNPACKED = 1
 P3R_EXT_UNPINNED_W32_DEFAULTS = 2   # the built-in width-32 constants are self-generated: using them is an explicit choice (p3r.h)
 P3R_EXT_ZK_DETERMINISTIC = 4        # ZK key taken as it is, p3r_zk_set_nonce allowed: reproducible proofs (tests, replay)
@@ -203,6 +204,8 @@ SIGNATURES = {
     "p3r_coset_lde_dmat": (vp, [vp, vp, C.c_uint32, C.c_uint32]),
     "p3r_dft": (C.c_int, [vp, u32p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
     "p3r_dft_batch_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
+    "p3r_open_points_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
+    "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_open": (C.c_int, [vp, vp, C.c_size_t, u32p, u32p]),

@@ -593,6 +593,60 @@ int p3r_dft(p3r_ctx* ctx, const uint32_t* rowmajor_in, size_t h, size_t w, uint3
   });
 }
 
+// The value half of Pcs::open (TwoAdicFriPcs::open's interpolate_coset loop): tu_open.hip
+static void open_points_check_modes(uint32_t added_bits, uint32_t eval_order, const size_t* point_offsets) {
+  if (eval_order != P3R_DFT_NATURAL && eval_order != P3R_DFT_BITREV) fail(P3R_EINVAL, "unknown evaluation order %u", eval_order);
+  if (added_bits > 31) fail(P3R_EINVAL, "added_bits (%u) out of range", added_bits);
+  if (!point_offsets) fail(P3R_EINVAL, "point_offsets is NULL");
+}
+int p3r_open_points_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats, uint32_t added_bits, uint32_t shift,
+                         uint32_t eval_order, const size_t* point_offsets, const uint32_t* points, uint32_t* values_out) {
+  return guard(ctx, [&] {
+    if (n_mats == 0) return;
+    if (!mats) fail(P3R_EINVAL, "mats is NULL");
+    open_points_check_modes(added_bits, eval_order, point_offsets);
+    std::vector<OpenPointsItem> items(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
+      items[i] = {mats[i]->d, mats[i]->h, mats[i]->w, point_offsets[i], point_offsets[i + 1]};
+    }
+    P3R_FIELD_CALL(ctx, open_points, ctx, items, (int)added_bits, shift, eval_order == P3R_DFT_BITREV, points, values_out);
+  });
+}
+int p3r_open_points(p3r_ctx* ctx, const p3r_matrix* mats, size_t n_mats, uint32_t added_bits, uint32_t shift,
+                    uint32_t eval_order, const size_t* point_offsets, const uint32_t* points, uint32_t* values_out) {
+  return guard(ctx, [&] {
+    if (n_mats == 0) return;
+    if (!mats) fail(P3R_EINVAL, "mats is NULL");
+    open_points_check_modes(added_bits, eval_order, point_offsets);
+    const uint32_t p = ctx->cfg.field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
+    std::vector<OpenPointsItem> items(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      items[i] = {nullptr, mats[i].height, mats[i].width, point_offsets[i], point_offsets[i + 1]};
+      log2_exact(mats[i].height, "matrix height");
+      if (mats[i].width && !mats[i].values) fail(P3R_EINVAL, "matrix %zu has no values", i);
+      for (size_t k = 0; k < mats[i].height * mats[i].width; ++k)
+        if (mats[i].values[k] >= p) fail(P3R_EINVAL, "matrix %zu: non-canonical field element at word %zu", i, k);
+    }
+    // what the device form refuses, before any matrix is uploaded (all widths 0: every check runs, nothing is launched)
+    {
+      std::vector<OpenPointsItem> dry = items;
+      for (auto& it : dry) it.w = 0;
+      P3R_FIELD_CALL(ctx, open_points, ctx, dry, (int)added_bits, shift, eval_order == P3R_DFT_BITREV, points, values_out);
+    }
+    std::vector<std::unique_ptr<p3r_dmat>> up(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (mats[i].width == 0 || point_offsets[i] == point_offsets[i + 1]) {   // contributes nothing
+        items[i].w = 0;
+        continue;
+      }
+      up[i] = P3R_FIELD_CALL(ctx, upload, ctx, mats[i].values, mats[i].height, mats[i].width);
+      items[i].d = up[i]->d;
+    }
+    P3R_FIELD_CALL(ctx, open_points, ctx, items, (int)added_bits, shift, eval_order == P3R_DFT_BITREV, points, values_out);
+  });
+}
+
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,
                          uint32_t* cap_out, p3r_tree** tree_out) {
   return guard(ctx, [&] {

@@ -64,6 +64,21 @@ std::vector<std::unique_ptr<p3r_dmat>> dft_batch(p3r_ctx* ctx, const std::vector
 template <class PP>
 void lde_init(p3r_ctx* ctx);
 
+// The value half of TwoAdicFriPcs::open (tu_open.hip): every column of each matrix at its points, over the context's
+// challenge field.  `d`: h x w, column-major Montgomery (null when w == 0).  The evaluations of the interpolant are rows
+// 0 .. h >> added_bits (bit_reversed: the low coset of a bit-reversed LDE) or rows k << added_bits (natural order), over
+// shift * <w_{h >> added_bits}> in that order; shift 0 = the field's generator.  Points p0 .. p1 of `points` (canonical,
+// DC words each) belong to the matrix, and p0 of a matrix is p1 of the one before.  values_out (host): [matrix][point]
+// [column][DC], canonical.  Everything that is refused is refused before anything is allocated or launched.
+struct OpenPointsItem {
+  const uint32_t* d;
+  size_t h, w;
+  size_t p0, p1;
+};
+template <class PP>
+void open_points(p3r_ctx* ctx, const std::vector<OpenPointsItem>& items, int added_bits, uint32_t shift, bool bit_reversed,
+                 const uint32_t* points, uint32_t* values_out);
+
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>
 void launch_logup_aux(p3r_ctx* ctx, unsigned blocks, const LogupJob* d_jobs, int n_jobs, const LookupChT<DC>& lc);

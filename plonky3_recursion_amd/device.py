@@ -6,6 +6,7 @@ Names follow the reference's traits where one exists:
   MerkleTree.commit/open_batch   p3_commit::Mmcs::{commit, open_batch}
   coset_lde_batch       p3_dft::TwoAdicSubgroupDft::coset_lde_batch (+ bit_reverse_rows)
   dft_batch             p3_dft::TwoAdicSubgroupDft::{dft_batch, idft_batch, coset_dft_batch, coset_idft_batch}
+  open_points           the opened values of p3_fri::TwoAdicFriPcs::open (interpolate_coset on the committed LDEs)
   permute_batch         CryptographicPermutation<[F;16]>::permute over a batch
   generate_trace_rows   Poseidon2CircuitAir::generate_trace_rows (poseidon2-circuit-air/src/air.rs:280)
 """
@@ -361,6 +362,44 @@ class Context:
         if len(shifts) != n:
             raise P3rError(-1, "one shift per matrix")
         return [int(s) for s in shifts]
+
+    # ---- the value half of Pcs::open
+    def open_points(self, mats, points, added_bits=0, shift=None, bit_reversed=True):
+        """The opened values of TwoAdicFriPcs::open over host matrices (2-D uint32 arrays, canonical): every column of
+        mats[i] - rows 0 .. h >> added_bits of a bit-reversed LDE (`bit_reversed`), or rows k << added_bits of a
+        natural-order one, taken as evaluations over shift * <w> - at the points points[i], a (k_i, DC) array of
+        canonical words (DC = the context's challenge degree).  `shift` None: the field's generator.  Returns a list of
+        (k_i, w_i, DC) arrays.  A point in the evaluation coset is refused (P3R_EINVAL)."""
+        keep = []
+        arr = (_lib.P3rMatrix * max(1, len(mats)))()
+        for i, m in enumerate(mats):
+            a, p = _u32(m)
+            assert a.ndim == 2
+            keep.append(a)
+            arr[i].values, arr[i].height, arr[i].width = p, a.shape[0], a.shape[1]
+        return self._open_points(self.lib.p3r_open_points, arr, [a.shape[1] for a in keep], points, added_bits, shift, bit_reversed)
+
+    def open_points_device(self, dmats, points, added_bits=0, shift=None, bit_reversed=True):
+        """The same over DeviceMatrix handles (what coset_lde_batch_device returns and commit_device commits): all
+        matrices and points in one call - one weights launch, one dot launch, one reduce launch, one wait."""
+        arr = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+        return self._open_points(self.lib.p3r_open_points_dmat, arr, [d.shape[1] for d in dmats], points, added_bits, shift, bit_reversed)
+
+    def _open_points(self, fn, arr, widths, points, added_bits, shift, bit_reversed):
+        n, dc = len(widths), self.challenge_degree
+        if len(points) != n:
+            raise P3rError(-1, "one array of points per matrix")
+        pts = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1, dc) for p in points]
+        offs = (C.c_size_t * (n + 1))(*np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64).tolist())
+        flat, fp = _u32(np.concatenate(pts + [np.empty((0, dc), dtype=np.uint32)]))
+        out = np.empty(sum(len(p) * w for p, w in zip(pts, widths)) * dc, dtype=np.uint32)
+        self.check(fn(self.h, arr, n, added_bits, 0 if shift is None else int(shift),
+                      _lib.P3R_DFT_BITREV if bit_reversed else _lib.P3R_DFT_NATURAL, offs, fp, out.ctypes.data_as(_lib.u32p)))
+        res, at = [], 0
+        for p, w in zip(pts, widths):
+            res.append(out[at:at + len(p) * w * dc].reshape(len(p), w, dc))
+            at += len(p) * w * dc
+        return res
 
     # ---- MMCS
     def commit(self, mats):
