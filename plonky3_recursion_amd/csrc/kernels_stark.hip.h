@@ -1,7 +1,7 @@
 // gfx950 kernels for the proving stages after the main-trace commit:
 //   K7  LogUp auxiliary (permutation) trace       k_logup_aux, k_ef_scan
 //   K8  quotient evaluation                        k_quotient
-//   K9  openings at zeta / zeta*g                   k_bary_weights, k_open_dot, k_open_reduce
+//   K9  openings at zeta / zeta*g                   inv4 here; k_bary_weights, k_open_dot, k_open_reduce in kernels_open.hip.h
 //   K10 FRI reduced openings, folds, grinding       k_fri_fold, k_grind (reduced openings: kernels_fri_reduce.hip.h)
 //   query answers                                   k_gather
 // Protocol anchors are listed in p3r_prove.hip next to the host code that sequences them.
@@ -362,11 +362,7 @@ k_quotient(const QuotientArgs* __restrict__ jobs, int n_jobs, LookupChT<DC> lc, 
   for (int k = 0; k < DC; ++k) as_global(q.out)[((size_t)c * DC + k) * n + r] = quot.c[k].v;
 }
 
-// ------------------------------------------------------------------ K9: openings
-// All openings of one proof run as three launches over job lists (a recursion layer opens ~20
-// matrices at 1-2 points each; per-matrix launches are latency-bound for 2^14..2^16-row layers).
-// A block finds its job by walking the (short) list of first-block indices.
-//
+// ------------------------------------------------------------------ K9: openings (the kernels: kernels_open.hip.h)
 // Inverses of four extension elements with ONE base-field inversion (Montgomery's trick on their
 // norms): the tower inverse costs ~25 products plus a ~56-product exponentiation in the base
 // field, and the latter is what the four share.  A zero among them (never, for z outside the base
@@ -423,155 +419,12 @@ __device__ __forceinline__ void inv4(const Fp4<PP> (&x)[4], Fp4<PP> (&out)[4]) {
   out[3] = x[3].inv_given(nm[3], i3);
 }
 
-// Barycentric weights over the trace subgroup:  L_i(z) = w^i (z^n - 1) / (n (z - w^i)).
-// `scale` = (z^n - 1)/n is supplied by the host.
-template <int DC>
-struct BaryJobT {
-  uint32_t* out;  // [DC][n]
-  uint64_t n;
-  uint32_t w_n;
-  EW<DC> z, scale;
-  uint32_t block0;  // first block of this job
-};
-using BaryJob = BaryJobT<4>;
-template <class PP, int DC = 4>
-__global__ void __launch_bounds__(kBlock) k_bary_weights(const BaryJobT<DC>* __restrict__ jobs, int n_jobs) {
-  using F = Fp<PP>;
-  using E = typename Chal<PP, DC>::type;
-  const int j = find_job(jobs, n_jobs);
-  const BaryJobT<DC>& b = jobs[j];
-  // four consecutive points per lane: their inversions share one base-field inversion (inv4)
-  const size_t i0 = ((size_t)(blockIdx.x - b.block0) * kBlock + threadIdx.x) * 4;
-  if (i0 >= b.n) return;
-  const F w1 = F::raw(b.w_n);
-  const E z = e4_load<PP, DC>(b.z), scale = e4_load<PP, DC>(b.scale);
-  F wi[4];
-  E x[4], inv[4];
-  wi[0] = w1.pow(i0);
-#pragma unroll
-  for (int m = 1; m < 4; ++m) wi[m] = wi[m - 1] * w1;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) x[m] = z - E::from_base(wi[m]);
-  inv4<PP>(x, inv);
-  const gptr<uint32_t> out = as_global(b.out);
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    if (i0 + m < b.n) {
-      const E r = inv[m] * scale * wi[m];
-#pragma unroll
-      for (int k = 0; k < DC; ++k) out[(size_t)k * b.n + i0 + m] = r.c[k].v;
-    }
-  }
-}
+}  // namespace p3r
 
-constexpr int kOpenCols = 8;      // matrix columns sharing one pass over the weights
-constexpr int kOpenRows = 8192;   // rows per block for tall matrices (the host shrinks it for short ones)
-struct OpenJob {
-  const uint32_t* mat;  // [w][n] column-major, natural order
-  const uint32_t *wt0, *wt1;  // weights per point ([DC][n]); wt1 null for a single point
-  uint32_t* partial;    // [P][n_chunks][w][DC]
-  uint64_t n;
-  int w, n_chunks, rows_per_block, col_groups;
-  uint32_t block0;      // first block of this job in the dot launch
-  uint32_t out0;        // first output word of this job ([P][w][DC]) in the reduce launch
-};
-// partial[p][chunk][col] = sum over the chunk's rows of weights_p[row] * M[col][row].
-// All accumulator indexing is compile-time (register resident); the block reduction is a
-// wave shuffle tree followed by a 4-wave LDS combine.
-template <class PP, int P, int DC>
-__device__ __forceinline__ void open_dot_block(const OpenJob& job, int col_group, int chunk,
-                                               uint32_t (*sh)[2 * kOpenCols * DC]) {
-  using F = Fp<PP>;
-  using E = typename Chal<PP, DC>::type;
-  constexpr int NV = P * kOpenCols * DC;
-  const gptr<const uint32_t> mat = as_global(job.mat);
-  const gptr<const uint32_t> wt0 = as_global(job.wt0);
-  const gptr<const uint32_t> wt1 = as_global(job.wt1);
-  const size_t n = job.n;
-  const int w = job.w, c0 = col_group * kOpenCols;
-  size_t r0 = (size_t)chunk * job.rows_per_block, r1 = r0 + job.rows_per_block < n ? r0 + job.rows_per_block : n;
-  E acc[P][kOpenCols];
-#pragma unroll
-  for (int p = 0; p < P; ++p)
-#pragma unroll
-    for (int c = 0; c < kOpenCols; ++c) acc[p][c] = E::zero();
-  // two rows per step: their products share one reduction per coefficient
-  for (size_t r = r0 + threadIdx.x; r < r1; r += 2 * kBlock) {
-    const size_t rb = r + kBlock;
-    const bool has_b = rb < r1;
-    E wa[P], wb[P];
-#pragma unroll
-    for (int k = 0; k < DC; ++k) {
-      wa[0].c[k] = F::raw(wt0[(size_t)k * n + r]);
-      wb[0].c[k] = has_b ? F::raw(wt0[(size_t)k * n + rb]) : F::zero();
-    }
-    if (P == 2)
-#pragma unroll
-      for (int k = 0; k < DC; ++k) {
-        wa[P - 1].c[k] = F::raw(wt1[(size_t)k * n + r]);
-        wb[P - 1].c[k] = has_b ? F::raw(wt1[(size_t)k * n + rb]) : F::zero();
-      }
-#pragma unroll
-    for (int c = 0; c < kOpenCols; ++c) {
-      const bool col = c0 + c < w;
-      const F ma = col ? F::raw(mat[(size_t)(c0 + c) * n + r]) : F::zero();
-      const F mb = col && has_b ? F::raw(mat[(size_t)(c0 + c) * n + rb]) : F::zero();
-#pragma unroll
-      for (int p = 0; p < P; ++p) acc[p][c] += E::dot2_base(wa[p], ma, wb[p], mb);
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int p = 0; p < P; ++p)
-#pragma unroll
-    for (int c = 0; c < kOpenCols; ++c)
-#pragma unroll
-      for (int k = 0; k < DC; ++k) {
-        F v = acc[p][c].c[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += F::raw(__shfl_down(v.v, off));
-        if (lane == 0) sh[wave][(p * kOpenCols + c) * DC + k] = v.v;
-      }
-  __syncthreads();
-  if ((int)threadIdx.x < NV) {
-    F s = F::zero();
-#pragma unroll
-    for (int wv = 0; wv < kBlock / 64; ++wv) s += F::raw(sh[wv][threadIdx.x]);
-    const int p = threadIdx.x / (kOpenCols * DC), rem = threadIdx.x % (kOpenCols * DC), c = rem / DC, k = rem % DC;
-    if (c0 + c < w) as_global(job.partial)[(((size_t)p * job.n_chunks + chunk) * w + c0 + c) * DC + k] = s.v;
-  }
-}
-template <class PP, int DC = 4>
-__global__ void __launch_bounds__(kBlock) k_open_dot(const OpenJob* __restrict__ jobs, int n_jobs) {
-  __shared__ uint32_t sh[kBlock / 64][2 * kOpenCols * DC];
-  const int j = find_job(jobs, n_jobs);
-  const OpenJob job = jobs[j];
-  const int local = (int)(blockIdx.x - job.block0);
-  const int col_group = local % job.col_groups, chunk = local / job.col_groups;
-  if (job.wt1) open_dot_block<PP, 2, DC>(job, col_group, chunk, sh);
-  else open_dot_block<PP, 1, DC>(job, col_group, chunk, sh);
-}
-// out[out0 + (p*w + c)*DC + k] = sum over chunks of partial[p][chunk][c][k]
-template <class PP, int DC = 4>
-__global__ void __launch_bounds__(kBlock)
-k_open_reduce(const OpenJob* __restrict__ jobs, int n_jobs, uint32_t total, uint32_t* __restrict__ out) {
-  using F = Fp<PP>;
-  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= total) return;
-  int j = 0, hi = n_jobs - 1;   // the last job whose first output is not past t (bisection: context.h::find_job)
-  while (j < hi) {
-    const int mid = (j + hi + 1) >> 1;
-    if (t >= jobs[mid].out0) j = mid; else hi = mid - 1;
-  }
-  const OpenJob& job = jobs[j];
-  const uint32_t local = t - job.out0;
-  const uint32_t per_point = (uint32_t)job.w * DC, p = local / per_point, rem = local % per_point;
-  F s = F::zero();
-  const gptr<const uint32_t> partial = as_global(job.partial);
-  for (int ch = 0; ch < job.n_chunks; ++ch)
-    s += F::raw(partial[((size_t)p * job.n_chunks + ch) * per_point + rem]);
-  out[t] = s.v;
-}
+// (k_bary_weights, k_open_dot / k_points_dot and k_open_reduce: one family for the prover and the public opening seam)
+#include "kernels_open.hip.h"
+
+namespace p3r {
 
 // ------------------------------------------------------------------ K10: FRI
 // One commit-phase fold of arity 2^LA (LA = 1..4): LA sequential arity-2 folds with beta, beta^2, ...

@@ -2,7 +2,9 @@
 // side by side (one unit took ten minutes): p3r_core.hip (C ABI, the Merkle tree module mmcs_impl.hip.h, prover
 // sequencing, circuit boundary),
 // tu_lde.hip (K5: NTT tables, passes and the coset LDE), tu_quotient.hip / tu_logup.hip (the two kernels with the
-// AIR constraint systems inlined, one instance per circuit degree and challenge degree), prep_device.hip.
+// AIR constraint systems inlined, one instance per circuit degree and challenge degree), tu_open.hip (K9 at the public
+// opening seam: it includes open_impl.hip.h, as p3r_core.hip does, for the planner OpenPlan and instantiates the K9
+// kernels of kernels_open.hip.h with the seam's entry point), prep_device.hip.
 // Kernels never call across units; only these host entry points do.
 #pragma once
 #include <memory>

@@ -3,7 +3,7 @@ value is f(z) = sum_k c_k z^k of KNOWN coefficients in the challenge field (test
 the library hold the evaluations of those polynomials, computed here from the definition (no FFT on this side), laid out
 as a committed LDE keeps them.  Every comparison is exact equality of canonical words.
 
-The dot kernel groups columns by eight for one or two points and by FOUR for three or four (tu_open.hip::pts_cols), so
+The dot kernel groups columns by eight for one or two points and by FOUR for three or four (kernels_open.hip.h::pts_cols), so
 the widths below go around both group widths: 3, 4, 5 and 7, 8, 9, plus 0, 1 and 17."""
 import functools
 import itertools

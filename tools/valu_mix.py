@@ -179,7 +179,7 @@ def main():
     out = {
         "provenance": "tools/valu_mix.py: static opcode histogram of the kernel instances of " + (stats_src or "?") +
                       " (disassembly of the built libp3r_hip.so, instances weighted by their time), priced with " + rate_src,
-        "kernel_sources_sha256": bench.kernel_source_digest(("kernels_ntt2.hip.h", "kernels_ntt.hip.h", "kernels_stark.hip.h", "air_device.hip.h")),
+        "kernel_sources_sha256": bench.kernel_source_digest(("kernels_ntt2.hip.h", "kernels_ntt.hip.h", "kernels_stark.hip.h", "kernels_open.hip.h", "air_device.hip.h")),
         "rates_T_per_s": rates,
         "families": fams,
     }
