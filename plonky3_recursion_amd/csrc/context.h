@@ -21,26 +21,13 @@
 #include <vector>
 
 #include "../../include/p3r.h"
+#include "error.h"
 #include "field.h"
 #include "poseidon2.h"
 #include "proof_layout.h"
 #include "mmcs4.h"
 
 namespace p3r {
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-[[noreturn]] inline void fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  throw Error(code, buf);
-}
 
 // fn(begin, end) over [0, n) on a few host threads (the preparation's per-op maps: validation, preprocessed rows,
 // the ALU matrix).  Chunks are contiguous and an error is reported for the LOWEST chunk that failed, so the message
@@ -571,12 +558,11 @@ struct p3r_ctx {
   // so after the first proof of a shape every table is already on the device.
   std::map<std::string, p3r::DevBuf> const_tables;
 
-  // NTT table caches (device), keyed by log size / direction / shift.
-  std::map<std::pair<int, int>, p3r::DevBuf> tw_sub;                 // (log_r, inverse)
-  std::map<std::pair<int, int>, std::pair<p3r::DevBuf, p3r::DevBuf>> tw4;  // (log_n, inverse) -> (lo, hi)
-  std::map<std::tuple<int, int, uint32_t>, std::pair<p3r::DevBuf, p3r::DevBuf>> pre;  // (log_n, added_bits, shift)
-  // coefficient scaling of the coset inverse transforms (tu_lde.hip::get_inv_pow); apart from `pre`, which the LDE reads
-  std::map<std::pair<int, uint32_t>, std::pair<p3r::DevBuf, p3r::DevBuf>> inv_pow;  // (log_n, shift)
+  // NTT table cache (device): two-level power tables (tu_lde.hip::power_table), keyed by (kind, log size, direction or
+  // added_bits, shift).  The kind is part of the key: the coefficient scaling of a coset inverse transform (NTT_INV_POW)
+  // never finds or replaces what the LDE reads (NTT_PRE).
+  struct NttTable { p3r::DevBuf lo, hi; };
+  std::map<std::tuple<int, int, int, uint32_t>, NttTable> ntt_tables;
 };
 
 // `words` cells from device memory into `dst` (host), for results the host transcript waits on.

@@ -9,13 +9,15 @@
 // 64-bit address arithmetic.  (rocprof, round 2: k_ntt_tile spends 10.7 VALU instructions per cell
 // and stage where the butterfly itself needs 5; profiles/r02/pmc_sq.json.)
 //
-// Tile: 2^13 cells = 512 lanes x 16 cells, four tiles per CU.
+// Tile: 2^13 cells = 512 lanes x 16 cells, four tiles per CU.  Which LOG_R / LOG_TILE a pass of a given height gets is
+// decided on the host by ntt_plan.h (the split, the tile rules and the LOG_R ranges instantiated); tu_lde.hip groups the
+// jobs of a batch by (log_r, log_tile) and launches one instance per group, or a mixed-size kernel for all of them.
 #pragma once
 #include "kernels_ntt.hip.h"
+#include "ntt_plan.h"  // kNtt2LogTile, kBitrevMinTiled and the rules that choose LOG_R / LOG_TILE for a pass
 
 namespace p3r {
 
-constexpr int kNtt2LogTile = 13;
 constexpr int kNtt2Lanes = 512;
 
 // w_{2^log_r}^idx in Montgomery form, at compile time (the twiddles of a last stage group are the
@@ -453,7 +455,6 @@ struct BitrevJob {
   uint32_t block0;    // a job owns columns << (log_n - 2*log_t) blocks (log_t = 0: one per column)
 };
 constexpr int kBitrevLanes = 256;
-constexpr int kBitrevMinTiled = 10;  // log_n from which the tiled form is used
 
 template <int LOG_T>
 __device__ __forceinline__ void bitrev_rows_tile(const BitrevJob& a, uint32_t local, uint32_t* tile) {

@@ -155,9 +155,10 @@ def test_round_trips_are_exact_and_leave_the_input_alone(ctxs, field, h, w):
 def test_mixed_batch_equals_single_calls(ctxs, field):
     ctx, p = ctxs(field), oracle_lib.MODULUS[field]
     rng = np.random.default_rng(4000)
-    shapes = [(1 << 13, 5), (1 << 14, 3), (1 << 7, 2), (1, 1)]
+    # 2^13, 2^14 and 2^15 rows: two column sizes (2^6, 2^7) and two line lengths (2^7, 2^8) in one batch - both mixed kernels
+    shapes = [(1 << 13, 5), (1 << 14, 3), (1 << 7, 2), (1, 1), (1 << 15, 2)]
     mats = [rng.integers(0, p, size=s, dtype=np.uint32) for s in shapes]
-    shifts = [oracle_lib.GENERATOR[field], 1, int(rng.integers(2, p)), int(rng.integers(2, p))]
+    shifts = [oracle_lib.GENERATOR[field], 1, int(rng.integers(2, p)), int(rng.integers(2, p)), int(rng.integers(2, p))]
     dms = [ctx.upload(m) for m in mats]
     for inverse in (False, True):
         for bit_reversed in (False, True):
