@@ -408,6 +408,52 @@ int p3r_open_points(p3r_ctx* ctx, const p3r_matrix* mats, size_t n_mats, uint32_
                     uint32_t eval_order, const size_t* point_offsets /* n_mats + 1 */, const uint32_t* points,
                     uint32_t* values_out);
 
+/* ---- the reduced openings of Pcs::open, and FriFoldingStrategy::fold_matrix with the roll-in ----
+ *
+ * The two deterministic steps of the second half of TwoAdicFriPcs::open: no transcript, no randomness, no proof bytes -
+ * alpha and beta are the caller's challenger's.  With p3r_coset_lde_dmat, p3r_mmcs_commit_dmat, p3r_open_points_dmat and
+ * p3r_mmcs_open_batch, what a caller still owns of the PCS is the challenger, the final polynomial (p3r_dft on the last,
+ * host-sized vector) and the commit-phase leaf view of a folded vector.
+ *
+ * p3r_fri_reduce_dmat == the reduced openings of Pcs::open.  Matrix i is a whole committed LDE: H_i x w_i, rows in
+ *                        bit-reversed order, row r at x_r = shift * w_{H_i}^bitrev(r); shift 0 = the field's generator.
+ *                        `points`: canonical words, DC per point; points point_offsets[i] .. point_offsets[i + 1] belong
+ *                        to matrix i.  `values` (HOST memory): [matrix][point][column][DC] canonical words, exactly what
+ *                        p3r_open_points_dmat wrote for the same matrices and points; `alpha`: DC canonical words.  The
+ *                        matrices are walked in call order and a matrix's points in order, with one running factor a_H
+ *                        per distinct height H, 1 at first; for each (matrix, point)
+ *                            ro_H[r] += a_H * sum_c alpha^c * (V_{i,p,c} - M_i[r][c]) / (z_{i,p} - x_r),
+ *                        then a_H *= alpha^{w_i} - the order of TwoAdicFriPcs::open.  outs (room for n_mats handles)
+ *                        receives one fresh H x DC matrix per distinct height that has a point, tallest first: column k
+ *                        is coefficient k and rows stay in the committed order (the flattening of dft_algebra_batch
+ *                        above); *n_outs says how many.  The caller frees them; inputs are never modified.  A matrix of
+ *                        width 0 or without points is legal and adds nothing; a matrix element is read once per call
+ *                        however many points its matrix has, and all heights share one launch.  The values need not be
+ *                        the matrices' own openings: every output word is the formula's.
+ *                        P3R_EINVAL, with a message, before anything is allocated or launched: n_mats == 0; a height
+ *                        that is not a power of two or is above 2^TWO_ADICITY; point_offsets that decrease; a
+ *                        non-canonical word in points, values, alpha or shift; values == NULL while a matrix has both
+ *                        points and columns; a point IN a matrix's evaluation coset (z^H == shift^H), where the quotient
+ *                        divides by zero - as p3r_open_points refuses it, so no wrong vector is returned.
+ * p3r_fri_fold_dmat   == FriFoldingStrategy::fold_matrix of TwoAdicFriFolding for log_arity = 1 .. 4, then the roll-in.
+ *                        `in`: n x DC, n = 2^L, row i the value at s_i = w_n^bitrev(i) (FRI folds over the subgroup: no
+ *                        shift).  Row r of the result is log_arity sequential arity-2 folds of rows r << log_arity ..
+ *                        (r + 1) << log_arity with beta, beta^2, beta^4, ..; one step is
+ *                            fold2(e0, e1, beta, x0) = (e0 + e1) / 2 + beta * (e0 - e1) / (2 * x0),  x0 the point of e0;
+ *                        with roll_in ((n >> log_arity) x DC; may be NULL), beta^(2^log_arity) * roll_in[r] is added.
+ *                        *out: a fresh (n >> log_arity) x DC matrix the caller frees; inputs are never modified.
+ *                        P3R_EINVAL: log_arity == 0, n < 2^log_arity, n not a power of two (or above 2^TWO_ADICITY), a
+ *                        width of `in` or roll_in other than DC, a roll_in of another height, a non-canonical beta word.
+ *                        P3R_EUNSUPPORTED: log_arity > 4, as in the prover.
+ * Both calls only enqueue on the context's stream; a refused call leaves the context usable. */
+int p3r_fri_reduce_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats, uint32_t shift,
+                        const size_t* point_offsets /* n_mats + 1 */, const uint32_t* points,
+                        const uint32_t* values /* [matrix][point][column][DC]: what p3r_open_points_dmat wrote */,
+                        const uint32_t* alpha /* DC canonical words */,
+                        p3r_dmat** outs /* room for n_mats */, size_t* n_outs);
+int p3r_fri_fold_dmat(p3r_ctx* ctx, const p3r_dmat* in, uint32_t log_arity, const uint32_t* beta /* DC */,
+                      const p3r_dmat* roll_in /* may be NULL */, p3r_dmat** out);
+
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *
  * p3r_prep_create  == ProverData::from_airs_and_degrees + CircuitProverData::new as called by

@@ -193,6 +193,49 @@ class CosetInterpolation {
     return res;
   }
 
+  // The reduced openings of TwoAdicFriPcs::open (p3r.h: p3r_fri_reduce_dmat): `mats` are whole committed LDEs, `values`
+  // what open_points returned for them at `points`, `alpha` the DC words of the batching challenge.  One H x DC matrix
+  // per distinct height that has a point, tallest first; the caller frees them.
+  std::vector<p3r_dmat*> reduced_openings(const Mats& mats, const Points& points, const std::vector<std::vector<uint32_t>>& values,
+                                          const std::vector<uint32_t>& alpha, uint32_t shift = 0) const {
+    const size_t dc = ctx_->config().challenge_degree ? ctx_->config().challenge_degree : 4;
+    if (points.size() != mats.size() || values.size() != mats.size() || alpha.size() != dc)
+      throw Error(P3R_EINVAL, "one list of points and one of values per matrix, DC words of alpha");
+    std::vector<size_t> offs(mats.size() + 1, 0);
+    std::vector<uint32_t> flat, vflat;
+    for (size_t i = 0; i < mats.size(); ++i) {
+      if (!mats[i] || points[i].size() % dc || values[i].size() != points[i].size() * p3r_dmat_width(mats[i]))
+        throw Error(P3R_EINVAL, "a NULL matrix, a point that is not DC words, or values that are not [point][column][DC]");
+      offs[i + 1] = offs[i] + points[i].size() / dc;
+      flat.insert(flat.end(), points[i].begin(), points[i].end());
+      vflat.insert(vflat.end(), values[i].begin(), values[i].end());
+    }
+    std::vector<p3r_dmat*> outs(mats.size(), nullptr);
+    size_t n_outs = 0;
+    ctx_->check(p3r_fri_reduce_dmat(ctx_->raw(), mats.data(), mats.size(), shift, offs.data(), flat.data(), vflat.data(), alpha.data(),
+                                    outs.data(), &n_outs));
+    outs.resize(n_outs);
+    return outs;
+  }
+
+ private:
+  const Context* ctx_;
+};
+
+// p3_fri::FriFoldingStrategy for TwoAdicFriFolding over device vectors (p3r.h: p3r_fri_fold_dmat): `in` is n x DC, row i
+// the value at w_n^bitrev(i); the result is the (n >> log_arity) x DC fold with beta (log_arity = 1 .. 4 sequential
+// arity-2 folds), plus beta^(2^log_arity) * roll_in when the next input height is rolled in.  The caller frees it.
+class TwoAdicFriFolding {
+ public:
+  explicit TwoAdicFriFolding(const Context& ctx) : ctx_(&ctx) {}
+  p3r_dmat* fold_matrix(const p3r_dmat* in, uint32_t log_arity, const std::vector<uint32_t>& beta, const p3r_dmat* roll_in = nullptr) const {
+    const size_t dc = ctx_->config().challenge_degree ? ctx_->config().challenge_degree : 4;
+    if (beta.size() != dc) throw Error(P3R_EINVAL, "beta is DC words");
+    p3r_dmat* out = nullptr;
+    ctx_->check(p3r_fri_fold_dmat(ctx_->raw(), in, log_arity, beta.data(), roll_in, &out));
+    return out;
+  }
+
  private:
   const Context* ctx_;
 };

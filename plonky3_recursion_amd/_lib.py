@@ -205,6 +205,9 @@ SIGNATURES = {
     "p3r_dft": (C.c_int, [vp, u32p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
     "p3r_dft_batch_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_uint32, u32p, C.c_uint32, C.POINTER(vp)]),
     "p3r_open_points_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
+    "p3r_fri_reduce_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p, u32p, C.POINTER(vp),
+                                      C.POINTER(C.c_size_t)]),
+    "p3r_fri_fold_dmat": (C.c_int, [vp, vp, C.c_uint32, u32p, vp, C.POINTER(vp)]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

@@ -647,6 +647,32 @@ int p3r_open_points(p3r_ctx* ctx, const p3r_matrix* mats, size_t n_mats, uint32_
   });
 }
 
+// The reduced openings of Pcs::open and FriFoldingStrategy::fold_matrix with the roll-in: tu_fri.hip
+int p3r_fri_reduce_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats, uint32_t shift, const size_t* point_offsets,
+                        const uint32_t* points, const uint32_t* values, const uint32_t* alpha, p3r_dmat** outs, size_t* n_outs) {
+  return guard(ctx, [&] {
+    if (n_outs) *n_outs = 0;
+    if (n_mats == 0) fail(P3R_EINVAL, "n_mats == 0: no matrix to reduce");
+    if (!mats || !point_offsets || !alpha || !outs || !n_outs) fail(P3R_EINVAL, "NULL argument");
+    std::vector<FriReduceItem> items(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
+      items[i] = {mats[i]->d, mats[i]->h, mats[i]->w, point_offsets[i], point_offsets[i + 1]};
+    }
+    auto res = P3R_FIELD_CALL(ctx, fri_reduce, ctx, items, shift, points, values, alpha);
+    for (size_t i = 0; i < res.size(); ++i) outs[i] = res[i].release();
+    *n_outs = res.size();
+  });
+}
+int p3r_fri_fold_dmat(p3r_ctx* ctx, const p3r_dmat* in, uint32_t log_arity, const uint32_t* beta, const p3r_dmat* roll_in,
+                      p3r_dmat** out) {
+  return guard(ctx, [&] {
+    if (out) *out = nullptr;
+    if (!in || !beta || !out) fail(P3R_EINVAL, "NULL argument");
+    *out = P3R_FIELD_CALL(ctx, fri_fold, ctx, in, log_arity, beta, roll_in).release();
+  });
+}
+
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,
                          uint32_t* cap_out, p3r_tree** tree_out) {
   return guard(ctx, [&] {

@@ -4,7 +4,9 @@
 // tu_lde.hip (K5: NTT tables, passes and the coset LDE), tu_quotient.hip / tu_logup.hip (the two kernels with the
 // AIR constraint systems inlined, one instance per circuit degree and challenge degree), tu_open.hip (K9 at the public
 // opening seam: it includes open_impl.hip.h, as p3r_core.hip does, for the planner OpenPlan and instantiates the K9
-// kernels of kernels_open.hip.h with the seam's entry point), prep_device.hip.
+// kernels of kernels_open.hip.h with the seam's entry point), tu_fri.hip (the reduced openings and the fold at the public
+// FRI seam: kernels_fri_points.hip.h, and its own instances of k_fri_inv_points, k_fri_vsum and k_fri_fold),
+// prep_device.hip.
 // Kernels never call across units; only these host entry points do.
 #pragma once
 #include <memory>
@@ -80,6 +82,23 @@ struct OpenPointsItem {
 template <class PP>
 void open_points(p3r_ctx* ctx, const std::vector<OpenPointsItem>& items, int added_bits, uint32_t shift, bool bit_reversed,
                  const uint32_t* points, uint32_t* values_out);
+
+// The reduced openings of Pcs::open and FriFoldingStrategy::fold_matrix with the roll-in (tu_fri.hip), over the context's
+// challenge field (DC words).  fri_reduce: `d` is a whole committed LDE, h x w, bit-reversed rows over shift * <w_h>
+// (null when w == 0; shift 0 = the field's generator); points p0 .. p1 of `points` belong to the matrix; `values` (host,
+// canonical) is [matrix][point][column][DC], what open_points wrote.  Returns one h x DC matrix per distinct height that
+// has a point, tallest first.  fri_fold: `in` n x DC over <w_n> in bit-reversed order -> (n >> log_arity) x DC.
+// Everything that is refused is refused before anything is allocated or launched; both only enqueue.
+struct FriReduceItem {
+  const uint32_t* d;
+  size_t h, w;
+  size_t p0, p1;
+};
+template <class PP>
+std::vector<std::unique_ptr<p3r_dmat>> fri_reduce(p3r_ctx* ctx, const std::vector<FriReduceItem>& items, uint32_t shift,
+                                                  const uint32_t* points, const uint32_t* values, const uint32_t* alpha);
+template <class PP>
+std::unique_ptr<p3r_dmat> fri_fold(p3r_ctx* ctx, const p3r_dmat* in, uint32_t log_arity, const uint32_t* beta, const p3r_dmat* roll_in);
 
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>

@@ -7,6 +7,8 @@ Names follow the reference's traits where one exists:
   coset_lde_batch       p3_dft::TwoAdicSubgroupDft::coset_lde_batch (+ bit_reverse_rows)
   dft_batch             p3_dft::TwoAdicSubgroupDft::{dft_batch, idft_batch, coset_dft_batch, coset_idft_batch}
   open_points           the opened values of p3_fri::TwoAdicFriPcs::open (interpolate_coset on the committed LDEs)
+  fri_reduce_device     the reduced openings of p3_fri::TwoAdicFriPcs::open (one vector per LDE height)
+  fri_fold_device       p3_fri::FriFoldingStrategy::fold_matrix of TwoAdicFriFolding, with the roll-in of the next height
   permute_batch         CryptographicPermutation<[F;16]>::permute over a batch
   generate_trace_rows   Poseidon2CircuitAir::generate_trace_rows (poseidon2-circuit-air/src/air.rs:280)
 """
@@ -400,6 +402,42 @@ class Context:
             res.append(out[at:at + len(p) * w * dc].reshape(len(p), w, dc))
             at += len(p) * w * dc
         return res
+
+    # ---- the reduced openings of Pcs::open, and FriFoldingStrategy::fold_matrix with the roll-in
+    def fri_reduce_device(self, dmats, points, values, alpha, shift=None):
+        """The per-height reduced openings FRI starts from: dmats[i] is a whole committed LDE (bit-reversed rows over
+        shift * <w>; `shift` None: the field's generator), points[i] its (k_i, DC) opening points, values[i] its
+        (k_i, w_i, DC) opened values - exactly what open_points_device returned for the same matrices and points - and
+        `alpha` the DC canonical words of the batching challenge.  Returns a list of (H, DC) DeviceMatrix, one per
+        distinct height that has a point, tallest first; column k is coefficient k, rows stay in the committed order."""
+        n, dc = len(dmats), self.challenge_degree
+        if len(points) != n or len(values) != n:
+            raise P3rError(-1, "one array of points and one of values per matrix")
+        pts = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1, dc) for p in points]
+        vals = [np.ascontiguousarray(v, dtype=np.uint32).reshape(-1) for v in values]
+        for d, p, v in zip(dmats, pts, vals):
+            if v.size != len(p) * d.shape[1] * dc:
+                raise P3rError(-1, "values of a matrix must be (points, width, DC)")
+        arr = (C.c_void_p * max(1, n))(*[d.h for d in dmats])
+        offs = (C.c_size_t * (n + 1))(*np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64).tolist())
+        flat, fp = _u32(np.concatenate(pts + [np.empty((0, dc), dtype=np.uint32)]))
+        vflat, vp = _u32(np.concatenate(vals + [np.empty(0, dtype=np.uint32)]))
+        al, ap = _u32(np.asarray(alpha, dtype=np.uint32).reshape(dc))
+        outs = (C.c_void_p * max(1, n))()
+        n_outs = C.c_size_t(0)
+        self.check(self.lib.p3r_fri_reduce_dmat(self.h, arr, n, 0 if shift is None else int(shift), offs, fp, vp, ap, outs,
+                                                C.byref(n_outs)))
+        return [DeviceMatrix(self, self.ptr(outs[i])) for i in range(n_outs.value)]
+
+    def fri_fold_device(self, dmat, log_arity, beta, roll_in=None):
+        """FriFoldingStrategy::fold_matrix of TwoAdicFriFolding, then the roll-in: `dmat` is (n, DC), row i the value at
+        w_n^bitrev(i); row r of the result is `log_arity` (1 .. 4) sequential arity-2 folds of rows r << log_arity ..
+        with beta, beta^2, beta^4, .., plus beta^(2^log_arity) * roll_in[r] when `roll_in` ((n >> log_arity, DC)) is
+        given.  Returns a new DeviceMatrix; the inputs are left as they are."""
+        b, bp = _u32(np.asarray(beta, dtype=np.uint32).reshape(self.challenge_degree))
+        out = C.c_void_p()
+        self.check(self.lib.p3r_fri_fold_dmat(self.h, dmat.h, log_arity, bp, None if roll_in is None else roll_in.h, C.byref(out)))
+        return DeviceMatrix(self, self.ptr(out.value))
 
     # ---- MMCS
     def commit(self, mats):
