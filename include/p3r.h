@@ -187,6 +187,7 @@ typedef struct p3r_config {
 typedef struct p3r_ctx p3r_ctx;
 typedef struct p3r_dmat p3r_dmat; /* device-resident matrix (power-of-two height) */
 typedef struct p3r_tree p3r_tree; /* device-resident MMCS prover data */
+typedef struct p3r_challenger p3r_challenger; /* host-side Fiat-Shamir transcript (DuplexChallenger) */
 
 /* ---- context ---- */
 p3r_ctx* p3r_create(const p3r_config* cfg);
@@ -411,9 +412,9 @@ int p3r_open_points(p3r_ctx* ctx, const p3r_matrix* mats, size_t n_mats, uint32_
 /* ---- the reduced openings of Pcs::open, and FriFoldingStrategy::fold_matrix with the roll-in ----
  *
  * The two deterministic steps of the second half of TwoAdicFriPcs::open: no transcript, no randomness, no proof bytes -
- * alpha and beta are the caller's challenger's.  With p3r_coset_lde_dmat, p3r_mmcs_commit_dmat, p3r_open_points_dmat and
- * p3r_mmcs_open_batch, what a caller still owns of the PCS is the challenger, the final polynomial (p3r_dft on the last,
- * host-sized vector) and the commit-phase leaf view of a folded vector.
+ * alpha and beta are the caller's challenger's.  With p3r_coset_lde_dmat, p3r_mmcs_commit_dmat, p3r_open_points_dmat,
+ * p3r_mmcs_open_batch and the entries of the next section (the challenger, the commit-phase leaf view, the final
+ * polynomial and the folding schedule), a caller owns nothing of the PCS any more: what it brings is its AIR.
  *
  * p3r_fri_reduce_dmat == the reduced openings of Pcs::open.  Matrix i is a whole committed LDE: H_i x w_i, rows in
  *                        bit-reversed order, row r at x_r = shift * w_{H_i}^bitrev(r); shift 0 = the field's generator.
@@ -453,6 +454,65 @@ int p3r_fri_reduce_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats
                         p3r_dmat** outs /* room for n_mats */, size_t* n_outs);
 int p3r_fri_fold_dmat(p3r_ctx* ctx, const p3r_dmat* in, uint32_t log_arity, const uint32_t* beta /* DC */,
                       const p3r_dmat* roll_in /* may be NULL */, p3r_dmat** out);
+
+/* ---- the rest of p3_fri::prover::prove_fri: challenger, commit-phase leaf view, final polynomial, folding schedule ----
+ *
+ * Functions are only added: P3R_ABI_VERSION stays as it is (no struct and no existing entry changes meaning).
+ *
+ * p3r_challenger == DuplexChallenger<F, Perm16, 16, 8> of circuit-prover/src/config.rs over the context's width-16
+ *                   Poseidon2 constants (recursion/src/challenger/circuit.rs:97-156, :337-430) - the transcript the
+ *                   prover itself runs.  Host state; only p3r_challenger_grind touches the device.  A handle belongs to
+ *                   the context that made it and must be freed before that context is destroyed.
+ *   _create / _clone / _free   a fresh transcript (all-zero sponge), an independent copy, the end of one.  NULL on
+ *                              failure (p3r_last_error of the context; of NULL for a NULL argument).
+ *   _observe(words, n)         n canonical base elements, in order.
+ *   _sample(out, n)            n base elements.
+ *   _sample_ext(out)           one challenge-field element: DC words, which are DC consecutive samples.
+ *   _sample_bits(bits, out)    the low `bits` bits of one sample.
+ *   _check_witness(bits, w, ok_out)  observes w and samples `bits` bits, as check_witness does: *ok_out = 1 when they are
+ *                              zero.  bits == 0: accepted, transcript untouched.
+ *   _grind(ctx, bits, w_out)   the prover's proof-of-work search on the device: the SMALLEST canonical witness the check
+ *                              accepts; the challenger is left in the post-check state.  bits == 0: witness 0, transcript
+ *                              untouched.
+ *   P3R_EINVAL with a message and the challenger's state unchanged: a non-canonical word (nothing of the call is
+ *   observed), bits > 30, a NULL handle or buffer, a challenger of another context.  On a NULL handle the message is
+ *   p3r_last_error(NULL)'s.
+ *
+ * p3r_fri_leaf_view_dmat  == the matrix ExtensionMmcs::commit_matrix commits in commit_phase.  `vec`: n x DC, n = 2^L, in
+ *                            the layout p3r_fri_fold_dmat takes.  *out: a fresh (n >> log_arity) x (DC << log_arity) matrix
+ *                            the caller frees; row r is the flattened extension elements r << log_arity ..
+ *                            (r + 1) << log_arity: column j * DC + k of row r is coefficient k of element
+ *                            (r << log_arity) + j.  A plain p3r_dmat: p3r_mmcs_commit_dmat commits it and
+ *                            p3r_mmcs_open_batch opens it, so both MMCS arities, the hiding MMCS and cap_height serve a
+ *                            commit phase as they are.  The proof's sibling_values of a query are the opened row without
+ *                            the element index & (2^log_arity - 1).  Refusals as p3r_fri_fold_dmat's, before anything is
+ *                            allocated: log_arity == 0, a width other than DC, n not a power of two (or above
+ *                            2^TWO_ADICITY) or n < 2^log_arity P3R_EINVAL; log_arity > 4 P3R_EUNSUPPORTED.  Only enqueues.
+ * p3r_fri_final_poly_dmat == the final polynomial: `vec` is m x DC, the last folded vector over <w_m> in bit-reversed
+ *                            order; coeffs_out (HOST) receives 2^log_final_poly_len x DC canonical words, the
+ *                            coefficients in natural order (the prover's own inverse DFT).  P3R_EINVAL: a non-zero
+ *                            coefficient at or above 2^log_final_poly_len (the prover's message: the input is not of low
+ *                            degree), m < 2^log_final_poly_len, m > 2^16 (the vector is fetched to the host; the cap keeps
+ *                            a misuse from downloading an LDE), a width other than DC.
+ * p3r_fri_log_arity       == the folding schedule the prover follows: log2 of the arity of commit phase `phase` at height
+ *                            2^log_cur, with the context's max_log_arity and fri_log_arities.  Without an explicit
+ *                            schedule: min(max_log_arity, log_cur - log_final, log_cur - log_next_input), at least 1 -
+ *                            fold as far as allowed without passing the next roll-in height (log_next_input; -1: none)
+ *                            or the final height.  With one: its entry when it is legal.  -1 where the schedule does
+ *                            not fit (or ctx is NULL). */
+p3r_challenger* p3r_challenger_create(p3r_ctx* ctx);
+p3r_challenger* p3r_challenger_clone(const p3r_challenger* ch);
+void p3r_challenger_free(p3r_challenger* ch);
+int p3r_challenger_observe(p3r_challenger* ch, const uint32_t* words, size_t n);
+int p3r_challenger_sample(p3r_challenger* ch, uint32_t* out, size_t n);
+int p3r_challenger_sample_ext(p3r_challenger* ch, uint32_t* out /* DC */);
+int p3r_challenger_sample_bits(p3r_challenger* ch, uint32_t bits, uint32_t* out);
+int p3r_challenger_check_witness(p3r_challenger* ch, uint32_t bits, uint32_t witness, int* ok_out);
+int p3r_challenger_grind(p3r_ctx* ctx, p3r_challenger* ch, uint32_t bits, uint32_t* witness_out);
+int p3r_fri_leaf_view_dmat(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_arity, p3r_dmat** out);
+int p3r_fri_final_poly_dmat(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_final_poly_len,
+                            uint32_t* coeffs_out /* 2^log_final_poly_len x DC */);
+int p3r_fri_log_arity(const p3r_ctx* ctx, size_t phase, int log_cur, int log_final, int log_next_input /* -1: none */);
 
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *

@@ -9,6 +9,7 @@
 //   CircuitProverData            circuit-prover/src/batch_stark_prover.rs:314-341
 //   NonPrimitiveTableEntry       :272-290        BatchStarkProof  :610-636 (+ validate :666-681)
 //   BatchStarkProver::{prove_all_tables, verify_all_tables}   :1203-1268
+//   DuplexChallenger, TwoAdicFriFolding, prove_fri   p3_challenger::DuplexChallenger, p3_fri::{TwoAdicFriFolding, prover::prove_fri}
 //   Circuit<EF> / CircuitRunner  circuit/src/circuit.rs:152-181, circuit/src/tables/runner.rs:22-253
 //   FriRecursionBackend          recursion/src/backend/fri.rs:113-128
 //   ProveNextLayerParams, RecursionInput, RecursionOutput, NextLayerPrepCache,
@@ -235,10 +236,164 @@ class TwoAdicFriFolding {
     ctx_->check(p3r_fri_fold_dmat(ctx_->raw(), in, log_arity, beta.data(), roll_in, &out));
     return out;
   }
+  // The matrix ExtensionMmcs::commit_matrix commits in a commit phase (p3r.h: p3r_fri_leaf_view_dmat): row r = the
+  // flattened elements r << log_arity .. (r + 1) << log_arity of `in`.  A plain matrix for p3r_mmcs_commit_dmat; the
+  // caller frees it.
+  p3r_dmat* leaf_view(const p3r_dmat* in, uint32_t log_arity) const {
+    p3r_dmat* out = nullptr;
+    ctx_->check(p3r_fri_leaf_view_dmat(ctx_->raw(), in, log_arity, &out));
+    return out;
+  }
 
  private:
   const Context* ctx_;
 };
+
+// DuplexChallenger<F, Perm16, 16, 8> of circuit-prover/src/config.rs over the context's Poseidon2 constants (p3r.h:
+// p3r_challenger).  Host state, except the proof-of-work search of grind.  Words are canonical.
+class DuplexChallenger {
+ public:
+  explicit DuplexChallenger(const Context& ctx) : ctx_(&ctx), h_(ctx.ptr(p3r_challenger_create(ctx.raw()))) {}
+  DuplexChallenger(const DuplexChallenger& o) : ctx_(o.ctx_), h_(o.ctx_->ptr(p3r_challenger_clone(o.h_))) {}   // Clone
+  DuplexChallenger& operator=(const DuplexChallenger&) = delete;
+  ~DuplexChallenger() { p3r_challenger_free(h_); }
+  void observe(uint32_t word) { observe(&word, 1); }
+  void observe(const std::vector<uint32_t>& words) { observe(words.data(), words.size()); }
+  void observe(const uint32_t* words, size_t n) { ctx_->check(p3r_challenger_observe(h_, words, n)); }
+  uint32_t sample() {
+    uint32_t v = 0;
+    ctx_->check(p3r_challenger_sample(h_, &v, 1));
+    return v;
+  }
+  std::vector<uint32_t> sample_ext() {   // DC words: DC consecutive samples
+    std::vector<uint32_t> e(ctx_->config().challenge_degree ? ctx_->config().challenge_degree : 4);
+    ctx_->check(p3r_challenger_sample_ext(h_, e.data()));
+    return e;
+  }
+  uint32_t sample_bits(uint32_t bits) {
+    uint32_t v = 0;
+    ctx_->check(p3r_challenger_sample_bits(h_, bits, &v));
+    return v;
+  }
+  bool check_witness(uint32_t bits, uint32_t witness) {
+    int ok = 0;
+    ctx_->check(p3r_challenger_check_witness(h_, bits, witness, &ok));
+    return ok != 0;
+  }
+  uint32_t grind(uint32_t bits) {   // the smallest witness; the challenger is left in the post-check state
+    uint32_t w = 0;
+    ctx_->check(p3r_challenger_grind(ctx_->raw(), h_, bits, &w));
+    return w;
+  }
+  p3r_challenger* raw() const { return h_; }
+
+ private:
+  const Context* ctx_;
+  p3r_challenger* h_;
+};
+
+// What p3_fri::prover::prove_fri returns, as canonical words.
+struct FriProof {
+  struct PhaseOpening {
+    std::vector<uint32_t> row;       // the opened leaf row: 2^log_arity elements of DC words (sibling_values: the row
+                                     // without element index & (arity - 1))
+    std::vector<uint32_t> salts;     // hiding MMCS: mmcs_salt_elems words; empty otherwise
+    std::vector<uint32_t> siblings;  // proof_len x 8
+  };
+  uint32_t log_max_height = 0;
+  std::vector<std::vector<uint32_t>> commit_phase_caps;   // per phase: (8 << cap_height) words
+  std::vector<uint32_t> commit_pow_witnesses, log_arities;
+  std::vector<uint32_t> final_poly;                       // 2^log_final_poly_len x DC
+  uint32_t query_pow_witness = 0;
+  std::vector<size_t> query_indices;
+  std::vector<std::vector<PhaseOpening>> query_openings;  // [query][phase]
+};
+
+// p3_fri::prover::prove_fri over the per-height reduced openings `inputs` (tallest first, strictly decreasing heights, as
+// CosetInterpolation::reduced_openings returns them), with public calls only: per commit phase the leaf view, its
+// commitment, the cap observed, the commit proof of work, beta, the fold with the roll-in of the next input; then the
+// final polynomial, the log arities, the query proof of work, the query indices and the opening of every phase tree at
+// every index.  The input-round openings stay the caller's (p3r_mmcs_open_batch on its own trees at query_indices); the
+// inputs are left as they are.
+inline FriProof prove_fri(const Context& ctx, DuplexChallenger& challenger, const std::vector<const p3r_dmat*>& inputs) {
+  const p3r_config& cfg = ctx.config();
+  const size_t dc = cfg.challenge_degree ? cfg.challenge_degree : 4;
+  if (inputs.empty()) throw Error(P3R_EINVAL, "prove_fri: no input vector");
+  std::vector<int> logs;
+  for (const p3r_dmat* m : inputs) {
+    if (!m) throw Error(P3R_EINVAL, "prove_fri: a NULL input");
+    int l = 0;
+    while ((size_t(1) << l) < p3r_dmat_height(m)) ++l;
+    if (!logs.empty() && l >= logs.back()) throw Error(P3R_EINVAL, "prove_fri: the inputs must be one vector per height, tallest first");
+    logs.push_back(l);
+  }
+  const int log_max = logs[0], log_final = (int)(cfg.log_final_poly_len + cfg.log_blowup);
+  FriProof proof;
+  proof.log_max_height = (uint32_t)log_max;
+  std::vector<p3r_dmat*> owned;   // leaf views and folded vectors
+  std::vector<p3r_tree*> trees;
+  struct Cleanup {
+    const Context& ctx; std::vector<p3r_dmat*>& owned; std::vector<p3r_tree*>& trees;
+    ~Cleanup() {
+      for (p3r_tree* t : trees) p3r_tree_free(ctx.raw(), t);
+      for (p3r_dmat* d : owned) p3r_dmat_free(ctx.raw(), d);
+    }
+  } cleanup{ctx, owned, trees};
+  const TwoAdicFriFolding folding(ctx);
+  const p3r_dmat* cur = inputs[0];
+  int log_cur = log_max;
+  size_t next = 1;
+  while (log_cur > log_final) {
+    const int la = p3r_fri_log_arity(ctx.raw(), trees.size(), log_cur, log_final, next < inputs.size() ? logs[next] : -1);
+    if (la < 0)
+      throw Error(P3R_EINVAL, "fri_log_arities does not fit the proof: phase " + std::to_string(trees.size()) + " at height 2^" +
+                                  std::to_string(log_cur));
+    if (la > 4) throw Error(P3R_EUNSUPPORTED, "max_log_arity > 4 is not supported");
+    owned.push_back(folding.leaf_view(cur, (uint32_t)la));
+    const p3r_dmat* view = owned.back();
+    std::vector<uint32_t> cap(size_t(8) << cfg.cap_height);
+    p3r_tree* tree = nullptr;
+    ctx.check(p3r_mmcs_commit_dmat(ctx.raw(), &view, 1, cap.data(), &tree));
+    trees.push_back(tree);
+    challenger.observe(cap);
+    proof.commit_phase_caps.push_back(std::move(cap));
+    proof.commit_pow_witnesses.push_back(challenger.grind(cfg.commit_pow_bits));
+    const std::vector<uint32_t> beta = challenger.sample_ext();
+    const bool roll = next < inputs.size() && logs[next] == log_cur - la;
+    owned.push_back(folding.fold_matrix(cur, (uint32_t)la, beta, roll ? inputs[next] : nullptr));
+    if (roll) ++next;
+    cur = owned.back();
+    log_cur -= la;
+    proof.log_arities.push_back((uint32_t)la);
+  }
+  if (next != inputs.size()) throw Error(P3R_EINVAL, "FRI: an input height was never rolled in");
+  proof.final_poly.resize((size_t(1) << cfg.log_final_poly_len) * dc);
+  ctx.check(p3r_fri_final_poly_dmat(ctx.raw(), cur, cfg.log_final_poly_len, proof.final_poly.data()));
+  challenger.observe(proof.final_poly);
+  challenger.observe(proof.log_arities);
+  proof.query_pow_witness = challenger.grind(cfg.query_pow_bits);
+  for (uint32_t q = 0; q < cfg.num_queries; ++q) proof.query_indices.push_back(challenger.sample_bits((uint32_t)log_max));
+  const size_t nq = proof.query_indices.size();
+  proof.query_openings.assign(nq, {});
+  uint32_t shift = 0;
+  for (size_t ph = 0; ph < trees.size(); ++ph) {
+    shift += proof.log_arities[ph];   // the phase's tree index: the query index without the bits folded so far and this phase's
+    std::vector<size_t> idx(nq);
+    for (size_t q = 0; q < nq; ++q) idx[q] = proof.query_indices[q] >> shift;
+    const size_t w = p3r_tree_total_width(trees[ph]), S = p3r_tree_salt_elems(trees[ph]) * p3r_tree_num_matrices(trees[ph]),
+                 pl = p3r_tree_proof_len(trees[ph]) * 8;
+    std::vector<uint32_t> rows(nq * w), salts(nq * S), sibs(nq * pl);
+    ctx.check(p3r_mmcs_open_batch(ctx.raw(), trees[ph], idx.data(), nq, rows.data(), S ? salts.data() : nullptr, sibs.data()));
+    for (size_t q = 0; q < nq; ++q) {
+      FriProof::PhaseOpening o;
+      o.row.assign(rows.begin() + q * w, rows.begin() + (q + 1) * w);
+      o.salts.assign(salts.begin() + q * S, salts.begin() + (q + 1) * S);
+      o.siblings.assign(sibs.begin() + q * pl, sibs.begin() + (q + 1) * pl);
+      proof.query_openings[q].push_back(std::move(o));
+    }
+  }
+  return proof;
+}
 
 struct TablePacking {
   uint32_t public_lanes = 1, alu_lanes = 3, horner_packed_steps = 4, recompose_lanes = 1, min_trace_height = 1;

@@ -208,6 +208,18 @@ SIGNATURES = {
     "p3r_fri_reduce_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p, u32p, C.POINTER(vp),
                                       C.POINTER(C.c_size_t)]),
     "p3r_fri_fold_dmat": (C.c_int, [vp, vp, C.c_uint32, u32p, vp, C.POINTER(vp)]),
+    "p3r_challenger_create": (vp, [vp]),
+    "p3r_challenger_clone": (vp, [vp]),
+    "p3r_challenger_free": (None, [vp]),
+    "p3r_challenger_observe": (C.c_int, [vp, u32p, C.c_size_t]),
+    "p3r_challenger_sample": (C.c_int, [vp, u32p, C.c_size_t]),
+    "p3r_challenger_sample_ext": (C.c_int, [vp, u32p]),
+    "p3r_challenger_sample_bits": (C.c_int, [vp, C.c_uint32, u32p]),
+    "p3r_challenger_check_witness": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
+    "p3r_challenger_grind": (C.c_int, [vp, vp, C.c_uint32, u32p]),
+    "p3r_fri_leaf_view_dmat": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(vp)]),
+    "p3r_fri_final_poly_dmat": (C.c_int, [vp, vp, C.c_uint32, u32p]),
+    "p3r_fri_log_arity": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

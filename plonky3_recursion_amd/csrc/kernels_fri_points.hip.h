@@ -81,4 +81,41 @@ k_fri_reduce_points(const FriReduceJob* __restrict__ jobs, int n_jobs, const Fri
   for (int k = 0; k < DC; ++k) as_global(job.ro)[(size_t)k * h + r] = acc.c[k].v;
 }
 
+// The commit-phase leaf view of a folded vector (p3r_fri_leaf_view_dmat): the (rows) x (DC << LA) matrix whose row r is
+// the flattened extension elements r << LA .. (r + 1) << LA of the n = rows << LA element vector - what
+// ExtensionMmcs::commit_matrix commits in commit_phase, and what the prover's commit_phase_leaves hashes through a
+// strided view.  A pure copy of Montgomery words, no arithmetic:
+//   out[(j * DC + k) * rows + r] = in[k * n + (r << LA) + j],   j < 2^LA, k < DC.
+// One lane owns row r of plane k = blockIdx.y.  It reads its 2^LA adjacent words as k_fri_fold does (16-byte loads, one
+// 8-byte load at LA = 1; the alignment argument is at the launch) and stores one word into each of the 2^LA columns
+// j * DC + k: in every one of those stores consecutive lanes write consecutive words.  No LDS.
+template <int DC, int LA>
+__global__ void __launch_bounds__(kBlock) k_fri_leaf_view(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t rows) {
+  static_assert(LA >= 1 && LA <= 4, "rows of 2, 4, 8 or 16 elements");
+  constexpr int ARITY = 1 << LA;
+  const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const int k = (int)blockIdx.y;
+  if (r >= rows) return;
+  const size_t n_in = rows << LA;
+  const gptr<const uint32_t> src = as_global(in) + (size_t)k * n_in + (r << LA);
+  uint32_t e[ARITY];
+  if constexpr (LA == 1) {
+    const fri_u32x2 v = *(gptr<const fri_u32x2>)src;
+    e[0] = v.x;
+    e[1] = v.y;
+  } else {
+#pragma unroll
+    for (int q = 0; q < ARITY / 4; ++q) {
+      const fri_u32x4 v = ((gptr<const fri_u32x4>)src)[q];
+      e[4 * q] = v.x;
+      e[4 * q + 1] = v.y;
+      e[4 * q + 2] = v.z;
+      e[4 * q + 3] = v.w;
+    }
+  }
+  const gptr<uint32_t> dst = as_global(out) + (size_t)k * rows + r;
+#pragma unroll
+  for (int j = 0; j < ARITY; ++j) dst[(size_t)j * DC * rows] = e[j];
+}
+
 }  // namespace p3r

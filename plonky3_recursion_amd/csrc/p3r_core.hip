@@ -276,6 +276,63 @@ void mmcs_commit_canonical(p3r_ctx* ctx, p3r_tree* tree, uint32_t* cap_out) {
   tree->total_width -= n_mats * S;  // words of opened_values per index: the caller's widths, without the salts
   for (size_t i = 0; i < cap.size(); ++i) cap_out[i] = Fp<PP>::raw(cap[i]).to_canonical();
 }
+
+// p3r_fri_final_poly_dmat: the prover's final polynomial of a caller's last folded vector, canonical
+template <class PP, int DC>
+void fri_final_poly_dc(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t lf, uint32_t* coeffs_out) {
+  if (vec->w != (size_t)DC) fail(P3R_EINVAL, "the folded vector must be %d words wide (it is %zu)", DC, vec->w);
+  const int log_m = log2_exact(vec->h, "height of the last folded vector");
+  if (log_m > 16) fail(P3R_EINVAL, "the last folded vector has 2^%d rows: the final polynomial is formed on the host, from at most 2^16", log_m);
+  if (lf > (uint32_t)log_m) fail(P3R_EINVAL, "the last folded vector has 2^%d rows, fewer than the 2^%u coefficients asked for", log_m, lf);
+  std::vector<uint32_t> raw((size_t)DC << log_m);
+  P3R_HIP(fetch_small(ctx, vec->d, raw.size(), raw.data()));
+  const auto coeffs = fri_final_poly<PP, DC>(raw.data(), log_m, lf);
+  for (size_t i = 0; i < coeffs.size(); ++i)
+    for (int k = 0; k < DC; ++k) coeffs_out[i * DC + k] = coeffs[i].c[k].to_canonical();
+}
+template <class PP>
+void fri_final_poly_canonical(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t lf, uint32_t* coeffs_out) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>) return fri_final_poly_dc<PP, 5>(ctx, vec, lf, coeffs_out);
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  fri_final_poly_dc<PP, 4>(ctx, vec, lf, coeffs_out);
+}
+}  // namespace
+
+// p3r_challenger: a thin handle around HostChallenger<PP, DC> (host_transcript.h), DC the context's challenge degree
+struct p3r_challenger {
+  p3r_ctx* ctx = nullptr;
+  int tag = 0;                // 0: KoalaBear, DC = 4; 1: KoalaBear, DC = 5; 2: BabyBear, DC = 4
+  std::vector<uint32_t> rc;   // the context's width-16 constants, Montgomery: what the HostChallenger points at
+  std::shared_ptr<void> impl;
+};
+namespace {
+template <class Fn>
+void challenger_visit(const p3r_challenger* ch, Fn&& fn) {
+  switch (ch->tag) {
+    case 0: fn(*static_cast<HostChallenger<KoalaBearParams, 4>*>(ch->impl.get())); break;
+    case 1: fn(*static_cast<HostChallenger<KoalaBearParams, 5>*>(ch->impl.get())); break;
+    default: fn(*static_cast<HostChallenger<BabyBearParams, 4>*>(ch->impl.get())); break;
+  }
+}
+// a fresh transcript, or a copy of src's (same tag), over ch's own copy of the constants
+inline void challenger_make(p3r_challenger* ch, const p3r_challenger* src) {
+  auto make = [&](auto tag) {
+    using C = decltype(tag);
+    auto c = std::make_shared<C>(ch->rc.data());
+    if (src) {
+      *c = *static_cast<const C*>(src->impl.get());
+      c->rc = ch->rc.data();
+    }
+    ch->impl = c;
+  };
+  switch (ch->tag) {
+    case 0: make(HostChallenger<KoalaBearParams, 4>(nullptr)); break;
+    case 1: make(HostChallenger<KoalaBearParams, 5>(nullptr)); break;
+    default: make(HostChallenger<BabyBearParams, 4>(nullptr)); break;
+  }
+}
 }  // namespace
 
 // =============================================================================== C ABI
@@ -671,6 +728,116 @@ int p3r_fri_fold_dmat(p3r_ctx* ctx, const p3r_dmat* in, uint32_t log_arity, cons
     if (!in || !beta || !out) fail(P3R_EINVAL, "NULL argument");
     *out = P3R_FIELD_CALL(ctx, fri_fold, ctx, in, log_arity, beta, roll_in).release();
   });
+}
+
+// The rest of prove_fri at the seam: the challenger (HostChallenger, host_transcript.h; grind_witness / k_grind for the
+// proof of work), the commit-phase leaf view (tu_fri.hip), the final polynomial (fri_final_poly) and the schedule rule.
+p3r_challenger* p3r_challenger_create(p3r_ctx* ctx) {
+  p3r_challenger* out = nullptr;
+  guard(ctx, [&] {
+    if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
+    auto ch = std::make_unique<p3r_challenger>();
+    ch->ctx = ctx;
+    ch->rc = ctx->rc_mont_host;
+    ch->tag = ctx->cfg.field == P3R_FIELD_KOALA_BEAR ? (ctx->cfg.challenge_degree == 5 ? 1 : 0) : 2;
+    challenger_make(ch.get(), nullptr);
+    out = ch.release();
+  });
+  return out;
+}
+p3r_challenger* p3r_challenger_clone(const p3r_challenger* src) {
+  p3r_challenger* out = nullptr;
+  guard(src ? src->ctx : nullptr, [&] {
+    if (!src) fail(P3R_EINVAL, "challenger is NULL");
+    auto ch = std::make_unique<p3r_challenger>();
+    ch->ctx = src->ctx;
+    ch->rc = src->rc;
+    ch->tag = src->tag;
+    challenger_make(ch.get(), src);
+    out = ch.release();
+  });
+  return out;
+}
+void p3r_challenger_free(p3r_challenger* ch) { delete ch; }
+int p3r_challenger_observe(p3r_challenger* ch, const uint32_t* words, size_t n) {
+  return guard(ch ? ch->ctx : nullptr, [&] {
+    if (!ch) fail(P3R_EINVAL, "challenger is NULL");
+    if (n && !words) fail(P3R_EINVAL, "words is NULL");
+    challenger_visit(ch, [&](auto& c) {
+      using F = typename std::decay_t<decltype(c)>::F;
+      for (size_t i = 0; i < n; ++i)   // all of them, before any is observed
+        if (words[i] >= F::P) fail(P3R_EINVAL, "non-canonical word %zu observed", i);
+      for (size_t i = 0; i < n; ++i) c.observe(F::from_canonical(words[i]));
+    });
+  });
+}
+int p3r_challenger_sample(p3r_challenger* ch, uint32_t* out, size_t n) {
+  return guard(ch ? ch->ctx : nullptr, [&] {
+    if (!ch) fail(P3R_EINVAL, "challenger is NULL");
+    if (n && !out) fail(P3R_EINVAL, "out is NULL");
+    challenger_visit(ch, [&](auto& c) {
+      for (size_t i = 0; i < n; ++i) out[i] = c.sample().to_canonical();
+    });
+  });
+}
+int p3r_challenger_sample_ext(p3r_challenger* ch, uint32_t* out) {
+  return guard(ch ? ch->ctx : nullptr, [&] {
+    if (!ch) fail(P3R_EINVAL, "challenger is NULL");
+    if (!out) fail(P3R_EINVAL, "out is NULL");
+    challenger_visit(ch, [&](auto& c) {
+      const auto e = c.sample_ext();
+      for (size_t k = 0; k < sizeof e.c / sizeof e.c[0]; ++k) out[k] = e.c[k].to_canonical();
+    });
+  });
+}
+int p3r_challenger_sample_bits(p3r_challenger* ch, uint32_t bits, uint32_t* out) {
+  return guard(ch ? ch->ctx : nullptr, [&] {
+    if (!ch) fail(P3R_EINVAL, "challenger is NULL");
+    if (!out) fail(P3R_EINVAL, "out is NULL");
+    if (bits > 30) fail(P3R_EINVAL, "sample_bits: bits must be <= 30 (got %u)", bits);
+    challenger_visit(ch, [&](auto& c) { *out = c.sample_bits((int)bits); });
+  });
+}
+int p3r_challenger_check_witness(p3r_challenger* ch, uint32_t bits, uint32_t witness, int* ok_out) {
+  return guard(ch ? ch->ctx : nullptr, [&] {
+    if (!ch) fail(P3R_EINVAL, "challenger is NULL");
+    if (!ok_out) fail(P3R_EINVAL, "ok_out is NULL");
+    if (bits > 30) fail(P3R_EINVAL, "proof-of-work bits must be <= 30");
+    challenger_visit(ch, [&](auto& c) {
+      using F = typename std::decay_t<decltype(c)>::F;
+      if (witness >= F::P) fail(P3R_EINVAL, "non-canonical proof-of-work witness");
+      *ok_out = c.check_witness((int)bits, F::from_canonical(witness)) ? 1 : 0;
+    });
+  });
+}
+int p3r_challenger_grind(p3r_ctx* ctx, p3r_challenger* ch, uint32_t bits, uint32_t* witness_out) {
+  return guard(ctx, [&] {
+    if (!ctx || !ch) fail(P3R_EINVAL, "ctx or challenger is NULL");
+    if (!witness_out) fail(P3R_EINVAL, "witness_out is NULL");
+    if (ch->ctx != ctx) fail(P3R_EINVAL, "the challenger belongs to another context");
+    if (bits > 30) fail(P3R_EINVAL, "proof-of-work bits must be <= 30");
+    challenger_visit(ch, [&](auto& c) {
+      using PP = typename std::decay_t<decltype(c)>::F::Params;
+      *witness_out = grind_witness<PP>(ctx, c, (int)bits).to_canonical();
+    });
+  });
+}
+int p3r_fri_leaf_view_dmat(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_arity, p3r_dmat** out) {
+  return guard(ctx, [&] {
+    if (out) *out = nullptr;
+    if (!vec || !out) fail(P3R_EINVAL, "NULL argument");
+    *out = P3R_FIELD_CALL(ctx, fri_leaf_view, ctx, vec, log_arity).release();
+  });
+}
+int p3r_fri_final_poly_dmat(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_final_poly_len, uint32_t* coeffs_out) {
+  return guard(ctx, [&] {
+    if (!vec || !coeffs_out) fail(P3R_EINVAL, "NULL argument");
+    P3R_FIELD_CALL(ctx, fri_final_poly_canonical, ctx, vec, log_final_poly_len, coeffs_out);
+  });
+}
+int p3r_fri_log_arity(const p3r_ctx* ctx, size_t phase, int log_cur, int log_final, int log_next_input) {
+  if (!ctx) return -1;
+  return fri_log_arity(ctx->fri_log_arities, phase, (int)ctx->cfg.max_log_arity, log_cur, log_final, log_next_input);
 }
 
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,

@@ -160,6 +160,41 @@ Fp<PP> grind_witness(p3r_ctx* ctx, Challenger& ch, int bits) {
   return w;
 }
 
+// The final polynomial of FRI (ProofState::final_polynomial, p3r_fri_final_poly_dmat): `raw` is the last folded vector as
+// fetched, [DC][m] Montgomery planes, m = 2^log_m values over <w_m> in bit-reversed order.  Returns the 2^log_final_poly_len
+// low coefficients in natural order; a non-zero coefficient above them is refused.
+template <class PP, int DC>
+std::vector<typename Chal<PP, DC>::type> fri_final_poly(const uint32_t* raw, int log_m, uint32_t log_final_poly_len) {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  const size_t m = size_t(1) << log_m;
+  // inverse DFT, decimation in time: the rows are already in bit-reversed order, the
+  // coefficients come out in natural order
+  std::vector<E> coeffs(m);
+  for (size_t i = 0; i < m; ++i)
+    for (int k = 0; k < DC; ++k) coeffs[i].c[k] = F::raw(raw[(size_t)k * m + i]);
+  const F w_inv = F::two_adic_generator(log_m).inv(), m_inv = F::from_u64(m).inv();
+  for (size_t len = 2; len <= m; len <<= 1) {
+    const F w_len = w_inv.pow(m / len);
+    for (size_t i = 0; i < m; i += len) {
+      F x = F::one();
+      for (size_t j = 0; j < len / 2; ++j) {
+        const E u = coeffs[i + j], v = coeffs[i + j + len / 2] * x;
+        coeffs[i + j] = u + v;
+        coeffs[i + j + len / 2] = u - v;
+        x *= w_len;
+      }
+    }
+  }
+  for (auto& c : coeffs) c = c * m_inv;
+  const size_t flen = size_t(1) << log_final_poly_len;
+  for (size_t i = flen; i < m; ++i)
+    if (!coeffs[i].is_zero())
+      fail(P3R_EINVAL, "FRI final polynomial has degree >= 2^%u: the traces do not satisfy the constraints", log_final_poly_len);
+  coeffs.resize(flen);
+  return coeffs;
+}
+
 inline int zk_codewords(const p3r_config& cfg) { return cfg.zk ? (cfg.num_random_codewords ? (int)cfg.num_random_codewords : 2) : 0; }
 
 // HidingFriPcs::commit on a batch of matrices (kernels_zk.hip.h): h x w -> 2h x (w + R) each, one launch.
@@ -968,31 +1003,7 @@ struct BatchProver {
           if (beta.c[k].v != betas[DC * pi + k]) fail(P3R_EHIP, "internal: device and host FRI transcripts disagree");
       }
     }
-    // inverse DFT, decimation in time: the rows are already in bit-reversed order, the
-    // coefficients come out in natural order
-    std::vector<E> coeffs(m);
-    for (size_t i = 0; i < m; ++i)
-      for (int k = 0; k < DC; ++k) coeffs[i].c[k] = F::raw(raw[(size_t)k * m + i]);
-    const F w_inv = F::two_adic_generator(log_cur).inv(), m_inv = F::from_u64(m).inv();
-    for (size_t len = 2; len <= m; len <<= 1) {
-      const F w_len = w_inv.pow(m / len);
-      for (size_t i = 0; i < m; i += len) {
-        F x = F::one();
-        for (size_t j = 0; j < len / 2; ++j) {
-          const E u = coeffs[i + j], v = coeffs[i + j + len / 2] * x;
-          coeffs[i + j] = u + v;
-          coeffs[i + j + len / 2] = u - v;
-          x *= w_len;
-        }
-      }
-    }
-    for (auto& c : coeffs) c = c * m_inv;
-    const size_t flen = size_t(1) << cfg.log_final_poly_len;
-    for (size_t i = flen; i < m; ++i)
-      if (!coeffs[i].is_zero())
-        fail(P3R_EINVAL, "FRI final polynomial has degree >= 2^%u: the traces do not satisfy the constraints",
-             cfg.log_final_poly_len);
-    final_poly.assign(coeffs.begin(), coeffs.begin() + flen);
+    final_poly = fri_final_poly<PP, DC>(raw.data(), log_cur, cfg.log_final_poly_len);
   }
 
   // ---- 8. queries: one gather launch for every opened row / sibling of every query

@@ -5,7 +5,8 @@
 // AIR constraint systems inlined, one instance per circuit degree and challenge degree), tu_open.hip (K9 at the public
 // opening seam: it includes open_impl.hip.h, as p3r_core.hip does, for the planner OpenPlan and instantiates the K9
 // kernels of kernels_open.hip.h with the seam's entry point), tu_fri.hip (the reduced openings and the fold at the public
-// FRI seam: kernels_fri_points.hip.h, and its own instances of k_fri_inv_points, k_fri_vsum and k_fri_fold),
+// FRI seam and the commit-phase leaf view: kernels_fri_points.hip.h, and its own instances of k_fri_inv_points, k_fri_vsum
+// and k_fri_fold),
 // prep_device.hip.
 // Kernels never call across units; only these host entry points do.
 #pragma once
@@ -99,6 +100,10 @@ std::vector<std::unique_ptr<p3r_dmat>> fri_reduce(p3r_ctx* ctx, const std::vecto
                                                   const uint32_t* points, const uint32_t* values, const uint32_t* alpha);
 template <class PP>
 std::unique_ptr<p3r_dmat> fri_fold(p3r_ctx* ctx, const p3r_dmat* in, uint32_t log_arity, const uint32_t* beta, const p3r_dmat* roll_in);
+// The commit-phase leaf matrix of a folded vector (tu_fri.hip): `vec` n x DC -> (n >> log_arity) x (DC << log_arity), row r
+// = the flattened elements r << log_arity .. (r + 1) << log_arity.  Refuses what fri_fold refuses; only enqueues.
+template <class PP>
+std::unique_ptr<p3r_dmat> fri_leaf_view(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_arity);
 
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>

@@ -9,6 +9,8 @@
 // order, a matrix's points in order, one running alpha power per height - is TwoAdicFriPcs::open's and
 // prove_impl.hip.h::fri_reduce's.
 // Fold: one launch of k_fri_fold (kernels_stark.hip.h), the kernel of the prover's commit phase.
+// Leaf view (p3r_fri_leaf_view_dmat): one launch of k_fri_leaf_view (kernels_fri_points.hip.h), a copy of the folded
+// vector into the matrix ExtensionMmcs commits in a commit phase, so that the public MMCS calls serve it as they are.
 #include <algorithm>
 #include <array>
 #include <map>
@@ -234,6 +236,34 @@ std::unique_ptr<p3r_dmat> fri_fold_dc(p3r_ctx* ctx, const p3r_dmat* in, uint32_t
   return out;
 }
 
+template <class PP, int DC>
+std::unique_ptr<p3r_dmat> fri_leaf_view_dc(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t la) {
+  // ---- everything that is refused, before anything is allocated or launched (the refusals of fri_fold_dc)
+  if (la == 0) fail(P3R_EINVAL, "log_arity must be at least 1");
+  if (la > 4) fail(P3R_EUNSUPPORTED, "log_arity > 4 is not supported");
+  const int log_n = log2_exact(vec->h, "height of the folded vector");
+  if (log_n > PP::TWO_ADICITY) fail(P3R_EINVAL, "2^%d rows exceed the field's two-adicity (%d)", log_n, PP::TWO_ADICITY);
+  if ((uint32_t)log_n < la) fail(P3R_EINVAL, "a vector of %zu rows has no rows of %u elements", vec->h, 1u << la);
+  if (vec->w != (size_t)DC) fail(P3R_EINVAL, "the folded vector must be %d words wide (it is %zu)", DC, vec->w);
+  const size_t rows = vec->h >> la;
+
+  auto out = dmat_alloc(rows, (size_t)DC << la);
+  // k_fri_leaf_view reads a lane's 2^la adjacent words of one plane with 16-byte loads (one 8-byte load at la = 1) at
+  // vec + k * n + (r << la) words.  For a caller's p3r_dmat that address is aligned: every handle owns a pool allocation
+  // (p3r_dmat::d is DevBuf::p, from hipMalloc at a multiple of 256 bytes - there are no borrowed views behind the
+  // ABI), a plane is n = 2^L >= 2^la words, so k * n and r << la are both multiples of 2^la words: of 16 bytes for
+  // la >= 2 and of 8 bytes for la = 1.  The last lane's load ends at the plane's end, never past the allocation; its
+  // last store is word (2^la * DC - 1) * rows + rows - 1, the last of the rows x (DC << la) result.
+  {
+    ProfScope ps(ctx, "fri_seam_leaf_view");
+    static constexpr void (*kView[4])(const uint32_t*, uint32_t*, size_t) = {k_fri_leaf_view<DC, 1>, k_fri_leaf_view<DC, 2>,
+                                                                             k_fri_leaf_view<DC, 3>, k_fri_leaf_view<DC, 4>};
+    hipLaunchKernelGGL(kView[la - 1], dim3(fri_blocks_for(rows), DC), dim3(kBlock), 0, ctx->stream, vec->d, out->d, rows);
+  }
+  P3R_HIP(hipGetLastError());
+  return out;
+}
+
 }  // namespace
 
 template <class PP>
@@ -254,11 +284,22 @@ std::unique_ptr<p3r_dmat> fri_fold(p3r_ctx* ctx, const p3r_dmat* in, uint32_t lo
   return fri_fold_dc<PP, 4>(ctx, in, log_arity, beta, roll_in);
 }
 
+template <class PP>
+std::unique_ptr<p3r_dmat> fri_leaf_view(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_arity) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>) return fri_leaf_view_dc<PP, 5>(ctx, vec, log_arity);
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  return fri_leaf_view_dc<PP, 4>(ctx, vec, log_arity);
+}
+
 template std::vector<std::unique_ptr<p3r_dmat>> fri_reduce<KoalaBearParams>(p3r_ctx*, const std::vector<FriReduceItem>&, uint32_t,
                                                                             const uint32_t*, const uint32_t*, const uint32_t*);
 template std::vector<std::unique_ptr<p3r_dmat>> fri_reduce<BabyBearParams>(p3r_ctx*, const std::vector<FriReduceItem>&, uint32_t,
                                                                            const uint32_t*, const uint32_t*, const uint32_t*);
 template std::unique_ptr<p3r_dmat> fri_fold<KoalaBearParams>(p3r_ctx*, const p3r_dmat*, uint32_t, const uint32_t*, const p3r_dmat*);
 template std::unique_ptr<p3r_dmat> fri_fold<BabyBearParams>(p3r_ctx*, const p3r_dmat*, uint32_t, const uint32_t*, const p3r_dmat*);
+template std::unique_ptr<p3r_dmat> fri_leaf_view<KoalaBearParams>(p3r_ctx*, const p3r_dmat*, uint32_t);
+template std::unique_ptr<p3r_dmat> fri_leaf_view<BabyBearParams>(p3r_ctx*, const p3r_dmat*, uint32_t);
 
 }  // namespace p3r

@@ -9,6 +9,9 @@ Names follow the reference's traits where one exists:
   open_points           the opened values of p3_fri::TwoAdicFriPcs::open (interpolate_coset on the committed LDEs)
   fri_reduce_device     the reduced openings of p3_fri::TwoAdicFriPcs::open (one vector per LDE height)
   fri_fold_device       p3_fri::FriFoldingStrategy::fold_matrix of TwoAdicFriFolding, with the roll-in of the next height
+  Challenger            DuplexChallenger<F, Perm16, 16, 8> (circuit-prover/src/config.rs), with the proof-of-work search
+  fri_leaf_view_device  the matrix ExtensionMmcs::commit_matrix commits in a FRI commit phase
+  prove_fri             p3_fri::prover::prove_fri (commit phase, final polynomial, query openings) from the calls above
   permute_batch         CryptographicPermutation<[F;16]>::permute over a batch
   generate_trace_rows   Poseidon2CircuitAir::generate_trace_rows (poseidon2-circuit-air/src/air.rs:280)
 """
@@ -439,6 +442,87 @@ class Context:
         self.check(self.lib.p3r_fri_fold_dmat(self.h, dmat.h, log_arity, bp, None if roll_in is None else roll_in.h, C.byref(out)))
         return DeviceMatrix(self, self.ptr(out.value))
 
+    # ---- the rest of prove_fri: challenger, commit-phase leaf view, final polynomial, schedule, and their composition
+    def challenger(self):
+        """A fresh DuplexChallenger over the context's width-16 Poseidon2 constants (p3r_challenger)."""
+        return Challenger(self, self.ptr(self.lib.p3r_challenger_create(self.h)))
+
+    def fri_leaf_view_device(self, dmat, log_arity):
+        """The commit-phase leaf matrix of the (n, DC) vector `dmat`: (n >> log_arity, DC << log_arity), row r the flattened
+        extension elements r << log_arity .. (r + 1) << log_arity - a plain DeviceMatrix for commit_device / open_many."""
+        out = C.c_void_p()
+        self.check(self.lib.p3r_fri_leaf_view_dmat(self.h, dmat.h, log_arity, C.byref(out)))
+        return DeviceMatrix(self, self.ptr(out.value))
+
+    def fri_final_poly_device(self, dmat, log_final_poly_len=None):
+        """The final polynomial of the last folded (m, DC) vector (bit-reversed over <w_m>): (2^log_final_poly_len, DC)
+        canonical coefficients in natural order.  Raises when a coefficient above them is not zero."""
+        lf = self.cfg.log_final_poly_len if log_final_poly_len is None else int(log_final_poly_len)
+        out = np.empty((1 << lf, self.challenge_degree), dtype=np.uint32)
+        self.check(self.lib.p3r_fri_final_poly_dmat(self.h, dmat.h, lf, out.ctypes.data_as(_lib.u32p)))
+        return out
+
+    def fri_log_arity(self, phase, log_cur, log_final, log_next_input=-1):
+        """log2 of the arity of commit phase `phase` at height 2^log_cur under the context's max_log_arity and
+        fri_log_arities (the prover's rule); -1 where the schedule does not fit."""
+        return int(self.lib.p3r_fri_log_arity(self.h, int(phase), int(log_cur), int(log_final), int(log_next_input)))
+
+    def prove_fri(self, challenger, inputs):
+        """p3_fri::prover::prove_fri over the per-height reduced openings `inputs` (tallest first, strictly decreasing
+        heights, as fri_reduce_device returns them), with public calls only: per commit phase the leaf view, its
+        commitment, the cap observed, the commit proof of work, beta, the fold with the roll-in of the next input; then
+        the final polynomial, the log arities, the query proof of work, the query indices and the opening of every phase
+        tree at every index.  The input-round openings stay the caller's (open_many on its own trees at
+        `query_indices`).  The inputs are left as they are.  Returns a FriProof."""
+        cfg, n_in = self.cfg, len(inputs)
+        if n_in == 0:
+            raise P3rError(-1, "prove_fri: no input vector")
+        logs = [int(d.shape[0]).bit_length() - 1 for d in inputs]
+        if any(a <= b for a, b in zip(logs, logs[1:])):
+            raise P3rError(-1, "prove_fri: the inputs must be one vector per height, tallest first")
+        log_max, log_final = logs[0], int(cfg.log_final_poly_len + cfg.log_blowup)
+        proof = FriProof(log_max_height=log_max)
+        cur, log_cur, nxt, trees, views, mine = inputs[0], log_max, 1, [], [], []
+        try:
+            while log_cur > log_final:
+                la = self.fri_log_arity(len(trees), log_cur, log_final, logs[nxt] if nxt < n_in else -1)
+                if la < 0:
+                    raise P3rError(-1, "fri_log_arities does not fit the proof: phase %d at height 2^%d" % (len(trees), log_cur))
+                if la > 4:
+                    raise P3rError(-5, "max_log_arity > 4 is not supported")
+                views.append(self.fri_leaf_view_device(cur, la))
+                cap, tree = self.commit_device([views[-1]])
+                trees.append(tree)
+                challenger.observe(cap.reshape(-1))
+                proof.commit_phase_caps.append(cap)
+                proof.commit_pow_witnesses.append(challenger.grind(cfg.commit_pow_bits))
+                beta = challenger.sample_ext()
+                roll = nxt < n_in and logs[nxt] == log_cur - la
+                folded = self.fri_fold_device(cur, la, beta, inputs[nxt] if roll else None)
+                mine.append(folded)
+                nxt += 1 if roll else 0
+                cur, log_cur = folded, log_cur - la
+                proof.log_arities.append(la)
+            if nxt != n_in:
+                raise P3rError(-1, "FRI: an input height was never rolled in")
+            proof.final_poly = self.fri_final_poly_device(cur)
+            challenger.observe(proof.final_poly.reshape(-1))
+            challenger.observe(proof.log_arities)
+            proof.query_pow_witness = challenger.grind(cfg.query_pow_bits)
+            proof.query_indices = [challenger.sample_bits(log_max) for _ in range(cfg.num_queries)]
+            per_phase, shift = [], 0
+            for la, tree in zip(proof.log_arities, trees):
+                shift += la   # the phase's tree index: the query index without the bits folded so far and this phase's
+                per_phase.append(tree.open_many([i >> shift for i in proof.query_indices]))
+            for q in range(len(proof.query_indices)):
+                proof.query_openings.append([FriPhaseOpening(o[q], None if s is None else s[q], pf[q]) for o, s, pf in per_phase])
+            return proof
+        finally:
+            for t in trees:
+                t.free()
+            for d in views + mine:
+                d.free()
+
     # ---- MMCS
     def commit(self, mats):
         """Mmcs::commit over host matrices (list of 2-D uint32 arrays). Returns (cap, tree)."""
@@ -527,6 +611,84 @@ class Context:
         ms = C.c_double()
         self.check(self.lib.p3r_time_permute_dmat(self.h, dmat.h, iters, C.byref(ms)))
         return ms.value
+
+
+class Challenger:
+    """DuplexChallenger<F, Perm16, 16, 8> over the context's Poseidon2 constants (p3r_challenger): host state, except the
+    proof-of-work search of `grind`.  Words are canonical."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def observe(self, words):
+        a, p = _u32(np.asarray(words, dtype=np.uint32).reshape(-1))
+        self.ctx.check(self.ctx.lib.p3r_challenger_observe(self.h, p, a.size))
+
+    def sample(self, n=None):
+        """One base element (an int), or `n` of them (an array)."""
+        out = np.empty(1 if n is None else int(n), dtype=np.uint32)
+        self.ctx.check(self.ctx.lib.p3r_challenger_sample(self.h, out.ctypes.data_as(_lib.u32p), out.size))
+        return int(out[0]) if n is None else out
+
+    def sample_ext(self):
+        """One challenge-field element: DC words (DC consecutive samples)."""
+        out = np.empty(self.ctx.challenge_degree, dtype=np.uint32)
+        self.ctx.check(self.ctx.lib.p3r_challenger_sample_ext(self.h, out.ctypes.data_as(_lib.u32p)))
+        return out
+
+    def sample_bits(self, bits):
+        out = C.c_uint32()
+        self.ctx.check(self.ctx.lib.p3r_challenger_sample_bits(self.h, int(bits), C.byref(out)))
+        return int(out.value)
+
+    def check_witness(self, bits, witness):
+        """Observes the witness and samples, as check_witness does; True when the low `bits` bits are zero."""
+        ok = C.c_int()
+        self.ctx.check(self.ctx.lib.p3r_challenger_check_witness(self.h, int(bits), int(witness), C.byref(ok)))
+        return bool(ok.value)
+
+    def grind(self, bits):
+        """The smallest canonical proof-of-work witness (device search); the challenger is left in the post-check state.
+        bits == 0: witness 0, transcript untouched."""
+        w = C.c_uint32()
+        self.ctx.check(self.ctx.lib.p3r_challenger_grind(self.ctx.h, self.h, int(bits), C.byref(w)))
+        return int(w.value)
+
+    def clone(self):
+        return Challenger(self.ctx, self.ctx.ptr(self.ctx.lib.p3r_challenger_clone(self.h)))
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.p3r_challenger_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class FriPhaseOpening:
+    """One commit-phase opening of a query: the opened leaf row (2^log_arity elements of DC words; the proof's
+    sibling_values are the row without element index & (arity - 1)), its salts (hiding MMCS; else None) and siblings."""
+
+    def __init__(self, row, salts, siblings):
+        self.row, self.salts, self.siblings = row, salts, siblings
+
+
+class FriProof:
+    """What p3_fri::prover::prove_fri returns (Context.prove_fri), as canonical words."""
+
+    def __init__(self, log_max_height=0):
+        self.log_max_height = log_max_height
+        self.commit_phase_caps = []      # per phase: (1 << cap_height, 8)
+        self.commit_pow_witnesses = []   # per phase
+        self.log_arities = []            # per phase
+        self.final_poly = None           # (2^log_final_poly_len, DC)
+        self.query_pow_witness = 0
+        self.query_indices = []
+        self.query_openings = []         # per query, per phase: FriPhaseOpening
 
 
 class DeviceMatrix:
