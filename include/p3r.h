@@ -514,6 +514,100 @@ int p3r_fri_final_poly_dmat(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_fina
                             uint32_t* coeffs_out /* 2^log_final_poly_len x DC */);
 int p3r_fri_log_arity(const p3r_ctx* ctx, size_t phase, int log_cur, int log_final, int log_next_input /* -1: none */);
 
+/* ---- the caller's AIR: constraint programs evaluated over the quotient domain of resident LDEs ----
+ *
+ * Functions are only added: P3R_ABI_VERSION stays as it is.
+ *
+ * The prover half of p3_uni_stark::prove between the trace commitment and the quotient commitment - quotient_values
+ * (Air::eval through ProverConstraintFolder on every row of the quotient domain, divided by the vanishing polynomial)
+ * followed by split_evals - for an AIR the CALLER brings.  Upstream's constraints are Rust trait code; here they are
+ * data, the straight-line program a SymbolicAirBuilder run of the same Air::eval would record.
+ *
+ * A program is an array of p3r_air_insn in SSA form: instruction i defines value i, and operands name EARLIER
+ * instructions only.  A value is a base-field element or a challenge-field element of DC words (DC = the context's
+ * challenge degree, 4 or 5); the type follows from the operands: base (op) base is base, anything with an extension
+ * operand is an extension value.
+ *
+ *   op                         operands                                   value
+ *   P3R_AIR_CONST              a = canonical base word                    base   (the enumerator of the table kinds
+ *   P3R_AIR_PUBLIC             a = index into public_values               base    below: 0 and 1 in both roles)
+ *   P3R_AIR_CHALLENGE          a = index into challenges (DC words each)  ext
+ *   P3R_AIR_LOCAL / _NEXT      a = matrix, b = column                     base: that cell of the current / next row
+ *   P3R_AIR_LOCAL_EXT / P3R_AIR_NEXT_EXT
+ *                              a = matrix, b = first of DC consecutive    ext: sum_k col[b + k] * X^k - how a
+ *                                  columns                                permutation / LogUp trace is stored flattened
+ *   P3R_AIR_IS_FIRST_ROW, P3R_AIR_IS_LAST_ROW, P3R_AIR_IS_TRANSITION
+ *                              none                                       base, defined below
+ *   P3R_AIR_ADD / _SUB / _MUL  a, b = value ids
+ *   P3R_AIR_NEG                a = value id
+ *   P3R_AIR_ASSERT_ZERO        a = value id                               none (it may not be referenced); constraint
+ *                                                                         number k is the k-th ASSERT_ZERO in program order
+ *
+ * Semantics.  h = trace height, q = log_quotient_degree, N = h * 2^q, shift 0 = the field's generator, w_m = the
+ * two-adic generator of order m.  All input matrices are committed LDEs of ONE height H = h << added_bits, rows in
+ * bit-reversed order as p3r_coset_lde_dmat writes them over shift * <w_H>, added_bits >= q; only their first N rows are
+ * read (they are the coset shift * <w_N> in bit-reversed order).  For the natural index i in [0, N):
+ *   x_i = shift * w_N^i; the current row is storage row bitrev_{log N}(i), the next row the storage row of
+ *   (i + 2^q) mod N (h = 1: the row itself);
+ *   is_transition = x - w_h^-1,  is_first_row = (x^h - 1) / (x - 1),  is_last_row = (x^h - 1) / (x - w_h^-1);
+ *   with n constraints C_0 .. C_{n-1}:  Q_i = (x_i^h - 1)^-1 * sum_k alpha^(n-1-k) * C_k(i)  - Horner in program order,
+ *   as ProverConstraintFolder accumulates.
+ * outs[c], c in [0, 2^q), is a fresh h x DC matrix the caller frees: row r is Q at i = r * 2^q + c, the point
+ * (shift * w_N^c) * w_h^r, in natural row order, column k coefficient k - what split_evals returns and what the
+ * prover's own quotient kernel writes.  Chunk c is therefore a matrix of evaluations over the coset (shift * w_N^c) * <w_h>;
+ * to extend it onto the commit coset G * <w_{h << added_bits}> (G the field's generator, as TwoAdicFriPcs::commit does with
+ * `GENERATOR / domain.shift()`), pass p3r_coset_lde_dmat(outs[c], added_bits, G / (shift * w_N^c)) - with the default
+ * shift that is w_N^-c - and commit the results with p3r_mmcs_commit_dmat.  The DFT seam takes a chunk as it is
+ * (P3R_DFT_INVERSE with shift * w_N^c, P3R_DFT_NATURAL, gives the chunk's coefficients).
+ *
+ * Degree rule of p3r_air_program_info: trace cells, is_first_row and is_last_row count 1; constants, publics, challenges
+ * and is_transition count 0; ADD / SUB take the maximum, MUL the sum, NEG its operand's.  The needed
+ * log_quotient_degree is log2_ceil(max(d, 2) - 1) for the largest constraint degree d.
+ *
+ * p3r_air_program_info (host only, no context: `cfg` gives the field and the challenge degree, as p3r_mmcs_verify takes
+ * it) validates a program against the matrix widths and reports n_constraints, max_degree, log_quotient_degree and
+ * peak_live, the most values alive at one instruction.  n_public / n_challenges are not known to it: indices are
+ * checked by p3r_quotient_program_dmat.  P3R_OK, or the refusal p3r_quotient_program_dmat would give for the program
+ * (message: p3r_last_error(NULL), as for a failed p3r_create).
+ *
+ * Refusals of p3r_quotient_program_dmat, with a message, before anything is allocated or launched.  P3R_EINVAL: an
+ * operand that is not an earlier value or is an ASSERT_ZERO; an unknown op; a matrix or column out of range (for _EXT:
+ * column + DC > width); a public or challenge index out of range; a non-canonical word anywhere (constants, publics,
+ * challenges, alpha, shift); no ASSERT_ZERO; matrices of different heights; added_bits < log_quotient_degree;
+ * log_quotient_degree below what the program needs; a height that is not a power of two, is below 2^added_bits or is
+ * above 2^TWO_ADICITY; a shift for which x^h - 1 has a zero in the quotient domain (shift^h a 2^q-th root of unity;
+ * shift^h == 1 is the case q = 0).  P3R_EUNSUPPORTED: more simultaneously live values than P3R_AIR_MAX_LIVE;
+ * log_quotient_degree > 4; zk contexts (their doubled domains are out of scope here).  A refused call leaves the
+ * context usable; the call only enqueues on the context's stream.
+ *
+ * P3R_AIR_MAX_LIVE: a lane of the interpreter keeps the live values of its row in LDS, [slot][word][lane] over the 64
+ * lanes of a one-wave workgroup: 256 bytes per base value, DC * 256 per extension value.  The two kinds have a slot
+ * region each, sized by the program's own peak, so the worst program (48 base values alive at one point, 48 quintic
+ * ones at another) takes 48 * (5 + 1) * 256 = 73,728 of the CU's 163,840 bytes - two workgroups per CU - while 48 live
+ * base values, one width-16 Poseidon2 round with its inputs, outputs and 16 temporaries, take 12 KiB (13 per CU). */
+enum {
+  P3R_AIR_CHALLENGE = 8, P3R_AIR_LOCAL = 9, P3R_AIR_NEXT = 10, P3R_AIR_LOCAL_EXT = 11, P3R_AIR_NEXT_EXT = 12,
+  P3R_AIR_IS_FIRST_ROW = 13, P3R_AIR_IS_LAST_ROW = 14, P3R_AIR_IS_TRANSITION = 15,
+  P3R_AIR_ADD = 16, P3R_AIR_SUB = 17, P3R_AIR_MUL = 18, P3R_AIR_NEG = 19, P3R_AIR_ASSERT_ZERO = 20
+};
+#define P3R_AIR_MAX_LIVE 48
+typedef struct p3r_air_insn {
+  uint32_t op, a, b;
+} p3r_air_insn;
+typedef struct p3r_air_info {
+  uint32_t n_constraints;
+  uint32_t max_degree;            /* the largest constraint degree under the rule above */
+  uint32_t log_quotient_degree;   /* the smallest the program may be evaluated with */
+  uint32_t peak_live;             /* <= P3R_AIR_MAX_LIVE for a program the device entry takes */
+} p3r_air_info;
+int p3r_air_program_info(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
+                         p3r_air_info* out);
+int p3r_quotient_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,
+                              uint32_t added_bits, uint32_t shift, uint32_t log_quotient_degree,
+                              const uint32_t* public_values, size_t n_public,
+                              const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
+                              const uint32_t* alpha /* DC */, p3r_dmat** outs /* 2^log_quotient_degree */);
+
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *
  * p3r_prep_create  == ProverData::from_airs_and_degrees + CircuitProverData::new as called by

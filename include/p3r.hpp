@@ -9,6 +9,7 @@
 //   CircuitProverData            circuit-prover/src/batch_stark_prover.rs:314-341
 //   NonPrimitiveTableEntry       :272-290        BatchStarkProof  :610-636 (+ validate :666-681)
 //   BatchStarkProver::{prove_all_tables, verify_all_tables}   :1203-1268
+//   AirProgram, quotient_values  p3_uni_stark::{SymbolicAirBuilder, prove's quotient_values + split_evals}
 //   DuplexChallenger, TwoAdicFriFolding, prove_fri   p3_challenger::DuplexChallenger, p3_fri::{TwoAdicFriFolding, prover::prove_fri}
 //   Circuit<EF> / CircuitRunner  circuit/src/circuit.rs:152-181, circuit/src/tables/runner.rs:22-253
 //   FriRecursionBackend          recursion/src/backend/fri.rs:113-128
@@ -248,6 +249,69 @@ class TwoAdicFriFolding {
  private:
   const Context* ctx_;
 };
+
+// The SymbolicAirBuilder of the seam (p3r.h: p3r_air_insn): an Air::eval written against this object records the
+// straight-line constraint program quotient_values evaluates.  A Value is the id of the instruction that defines it - a
+// base-field or challenge-field element, the type following from the operands; + - * and unary - record instructions.
+// Nothing is checked while building: info() (p3r_air_program_info, host only) and quotient_values validate a program.
+class AirProgram {
+ public:
+  struct Value {
+    AirProgram* prog;
+    uint32_t id;
+  };
+  Value constant(uint32_t canonical_word) { return emit(P3R_AIR_CONST, canonical_word); }
+  Value public_value(uint32_t index) { return emit(P3R_AIR_PUBLIC, index); }
+  Value challenge(uint32_t index) { return emit(P3R_AIR_CHALLENGE, index); }
+  Value local(uint32_t matrix, uint32_t column) { return emit(P3R_AIR_LOCAL, matrix, column); }
+  Value next(uint32_t matrix, uint32_t column) { return emit(P3R_AIR_NEXT, matrix, column); }
+  // the extension element stored flattened in DC consecutive columns from `column` on
+  Value local_ext(uint32_t matrix, uint32_t column) { return emit(P3R_AIR_LOCAL_EXT, matrix, column); }
+  Value next_ext(uint32_t matrix, uint32_t column) { return emit(P3R_AIR_NEXT_EXT, matrix, column); }
+  Value is_first_row() { return emit(P3R_AIR_IS_FIRST_ROW); }
+  Value is_last_row() { return emit(P3R_AIR_IS_LAST_ROW); }
+  Value is_transition() { return emit(P3R_AIR_IS_TRANSITION); }
+  void assert_zero(Value v) { emit(P3R_AIR_ASSERT_ZERO, v.id); }
+  Value emit(uint32_t op, uint32_t a = 0, uint32_t b = 0) {
+    insns_.push_back(p3r_air_insn{op, a, b});
+    return Value{this, (uint32_t)insns_.size() - 1};
+  }
+  const std::vector<p3r_air_insn>& insns() const { return insns_; }
+  // n_constraints, max_degree, the log_quotient_degree the program needs, peak_live - or the library's refusal
+  p3r_air_info info(const Context& ctx, const std::vector<size_t>& widths) const {
+    p3r_air_info out{};
+    const int rc = p3r_air_program_info(&ctx.config(), insns_.data(), insns_.size(), widths.data(), widths.size(), &out);
+    if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
+    return out;
+  }
+
+ private:
+  std::vector<p3r_air_insn> insns_;
+};
+inline AirProgram::Value operator+(AirProgram::Value a, AirProgram::Value b) { return a.prog->emit(P3R_AIR_ADD, a.id, b.id); }
+inline AirProgram::Value operator-(AirProgram::Value a, AirProgram::Value b) { return a.prog->emit(P3R_AIR_SUB, a.id, b.id); }
+inline AirProgram::Value operator*(AirProgram::Value a, AirProgram::Value b) { return a.prog->emit(P3R_AIR_MUL, a.id, b.id); }
+inline AirProgram::Value operator-(AirProgram::Value a) { return a.prog->emit(P3R_AIR_NEG, a.id); }
+
+// p3_uni_stark::prove's quotient_values followed by split_evals, over device matrices (p3r.h: p3r_quotient_program_dmat):
+// `mats` are the committed LDEs of the AIR's traces (one height, blow-up 2^added_bits, as Dft::coset_lde_batch returns
+// them over shift * <w>; shift 0 = the field's generator), `alpha` the DC words of the constraint-folding challenge,
+// `challenges` DC words per challenge the program reads.  Returns the 2^log_quotient_degree chunks, each h x DC in natural
+// order over (shift * w_N^c) * <w_h>; Dft::coset_lde_batch({chunk c}, added_bits, G / (shift * w_N^c)) extends chunk c onto
+// the commit coset.  The caller frees them; inputs are left as they are.
+inline std::vector<p3r_dmat*> quotient_values(const Context& ctx, const AirProgram& program, const std::vector<const p3r_dmat*>& mats,
+                                              uint32_t added_bits, uint32_t log_quotient_degree, const std::vector<uint32_t>& alpha,
+                                              const std::vector<uint32_t>& public_values = {}, const std::vector<uint32_t>& challenges = {},
+                                              uint32_t shift = 0) {
+  const size_t dc = ctx.config().challenge_degree ? ctx.config().challenge_degree : 4;
+  if (alpha.size() != dc || challenges.size() % dc) throw Error(P3R_EINVAL, "alpha is DC words, challenges DC words each");
+  if (log_quotient_degree > 4) throw Error(P3R_EUNSUPPORTED, "log_quotient_degree > 4 is not supported");
+  std::vector<p3r_dmat*> outs(size_t(1) << log_quotient_degree, nullptr);
+  ctx.check(p3r_quotient_program_dmat(ctx.raw(), program.insns().data(), program.insns().size(), mats.data(), mats.size(), added_bits,
+                                      shift, log_quotient_degree, public_values.data(), public_values.size(), challenges.data(),
+                                      challenges.size() / dc, alpha.data(), outs.data()));
+  return outs;
+}
 
 // DuplexChallenger<F, Perm16, 16, 8> of circuit-prover/src/config.rs over the context's Poseidon2 constants (p3r.h:
 // p3r_challenger).  Host state, except the proof-of-work search of grind.  Words are canonical.

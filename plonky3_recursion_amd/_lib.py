@@ -16,6 +16,11 @@ P3R_OPEN_POINTS_PER_PASS = 4              # p3r_open_points: points that share o
 P3R_EXT_LOOKUP_UNPACKED = 1
 P3R_EXT_UNPINNED_W32_DEFAULTS = 2   # the built-in width-32 constants are self-generated: using them is an explicit choice (p3r.h)
 P3R_EXT_ZK_DETERMINISTIC = 4        # ZK key taken as it is, p3r_zk_set_nonce allowed: reproducible proofs (tests, replay)
+# p3r_air_insn ops of the constraint-program seam (p3r_quotient_program_dmat) and the most values a program keeps alive
+(P3R_AIR_CONST, P3R_AIR_PUBLIC, P3R_AIR_CHALLENGE, P3R_AIR_LOCAL, P3R_AIR_NEXT, P3R_AIR_LOCAL_EXT, P3R_AIR_NEXT_EXT,
+ P3R_AIR_IS_FIRST_ROW, P3R_AIR_IS_LAST_ROW, P3R_AIR_IS_TRANSITION, P3R_AIR_ADD, P3R_AIR_SUB, P3R_AIR_MUL, P3R_AIR_NEG,
+ P3R_AIR_ASSERT_ZERO) = (0, 1) + tuple(range(8, 21))
+P3R_AIR_MAX_LIVE = 48
 FIELD_KOALA_BEAR = 0
 FIELD_BABY_BEAR = 1
 
@@ -75,6 +80,15 @@ class P3rP2wRows(C.Structure):   # rows of the width-32 Poseidon2 table (ABI 6)
 
 class P3rMatrix(C.Structure):
     _fields_ = [("values", C.POINTER(C.c_uint32)), ("height", C.c_size_t), ("width", C.c_size_t)]
+
+
+class P3rAirInsn(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32)]
+
+
+class P3rAirInfo(C.Structure):
+    _fields_ = [("n_constraints", C.c_uint32), ("max_degree", C.c_uint32), ("log_quotient_degree", C.c_uint32),
+                ("peak_live", C.c_uint32)]
 
 
 class P3rAirDesc(C.Structure):
@@ -220,6 +234,11 @@ SIGNATURES = {
     "p3r_fri_leaf_view_dmat": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(vp)]),
     "p3r_fri_final_poly_dmat": (C.c_int, [vp, vp, C.c_uint32, u32p]),
     "p3r_fri_log_arity": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    # the caller's AIR as a constraint program (quotient_values + split_evals on resident LDEs)
+    "p3r_air_program_info": (C.c_int, [C.POINTER(P3rConfig), C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
+                                       C.POINTER(P3rAirInfo)]),
+    "p3r_quotient_program_dmat": (C.c_int, [vp, C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, u32p, C.c_size_t, u32p, C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

@@ -1,0 +1,271 @@
+// The host half of the constraint-program seam (p3r_air_program_info, p3r_quotient_program_dmat; include/p3r.h): what is
+// decided about a caller's p3r_air_insn program before anything touches the device.  Host only, no HIP and no context:
+// tu_air.hip turns a plan into a launch, tests/air_program_host_main.cpp walks it with g++ alone.
+//
+//   air_plan      validation, typing (base / extension), the degree walk, liveness and the assignment of values to slots
+//   air_compile   the instruction stream the interpreter reads: operands as LDS word offsets, ops specialised by the
+//                 operand types, constants and public values in Montgomery form, challenges in a side table
+//   air_domain    the per-chunk constants of the quotient domain: x^h - 1 and its inverse on each of the 2^q cosets
+//
+// Slots.  A lane of k_quotient_program keeps the live values of its row in LDS, laid out [slot][word][lane].  Base values
+// take one word, extension values DC; each kind has a region of its own (extension slots first), so a freed slot fits
+// whatever is allocated next in its region and nothing fragments.  The assignment is a linear scan over last uses: the
+// operands that die at an instruction are released BEFORE its result is placed (the interpreter reads both operands
+// into registers first), lowest free slot first.  A region is as large as the most slots it ever held; the LDS of a
+// launch is sized by the program, not by P3R_AIR_MAX_LIVE.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <queue>
+#include <vector>
+
+#include "error.h"
+#include "field.h"
+
+namespace p3r {
+
+constexpr int kAirLanes = 64;          // lanes of a workgroup of k_quotient_program: one wave (kernels_air.hip.h)
+constexpr int kMaxAirDC = 5;           // words of the widest challenge field
+constexpr int kAirMaxLogChunks = 4;    // log_quotient_degree the entry takes
+// the largest slot file: every slot of both regions in use (P3R_AIR_MAX_LIVE base values at one point, as many extension values at another)
+constexpr size_t kAirMaxLdsBytes = (size_t)P3R_AIR_MAX_LIVE * (kMaxAirDC + 1) * kAirLanes * sizeof(uint32_t);
+constexpr uint32_t kAirNoSlot = 0xffffffffu;
+constexpr size_t kAirUnknownCount = ~size_t(0);   // n_public / n_challenges of p3r_air_program_info: not checked
+
+inline bool air_op_is_binary(uint32_t op) { return op == P3R_AIR_ADD || op == P3R_AIR_SUB || op == P3R_AIR_MUL; }
+inline bool air_op_known(uint32_t op) {
+  return op == P3R_AIR_CONST || op == P3R_AIR_PUBLIC || (op >= P3R_AIR_CHALLENGE && op <= P3R_AIR_ASSERT_ZERO);
+}
+// number of value operands
+inline int air_op_operands(uint32_t op) {
+  return air_op_is_binary(op) ? 2 : (op == P3R_AIR_NEG || op == P3R_AIR_ASSERT_ZERO) ? 1 : 0;
+}
+
+struct AirPlan {
+  p3r_air_info info{};
+  std::vector<uint8_t> is_ext;      // per value
+  std::vector<uint32_t> slot;       // per value: its slot in the region of its kind; kAirNoSlot for an ASSERT_ZERO
+  std::vector<uint32_t> last_use;   // per value: the last instruction that reads it (its own index: never read)
+  uint32_t n_base_slots = 0, n_ext_slots = 0;
+  bool uses_x = false;              // a selector: the lane needs its point x
+  bool uses_inv = false;            // is_first_row / is_last_row: the two inversions
+  // LDS word of a value's first word, and the words of a lane
+  uint32_t word_of(size_t v, int dc) const { return is_ext[v] ? slot[v] * (uint32_t)dc : n_ext_slots * (uint32_t)dc + slot[v]; }
+  uint32_t words(int dc) const { return n_ext_slots * (uint32_t)dc + n_base_slots; }
+  size_t lds_bytes(int dc) const { return (size_t)words(dc) * kAirLanes * sizeof(uint32_t); }
+};
+
+inline uint32_t air_log_quotient_degree(uint64_t max_degree) {
+  const uint64_t m = std::max<uint64_t>(max_degree, 2) - 1;
+  uint32_t l = 0;
+  while ((uint64_t(1) << l) < m) ++l;
+  return l;
+}
+
+// Everything that can be refused about a program on its own.  p: the field's modulus; dc: the challenge degree;
+// n_public / n_challenges: kAirUnknownCount leaves the indices unchecked; max_live: P3R_AIR_MAX_LIVE.
+inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths, size_t n_mats, int dc, uint32_t p,
+                        size_t n_public, size_t n_challenges, uint32_t max_live) {
+  if (n == 0 || !prog) fail(P3R_EINVAL, "the program has no ASSERT_ZERO (it is empty)");
+  if (n > 0x7fffffffu) fail(P3R_EINVAL, "the program is too long");
+  if (n_mats && !widths) fail(P3R_EINVAL, "widths is NULL");
+  constexpr uint64_t kDegCap = uint64_t(1) << 40;   // saturates: a chain of squarings must not wrap
+  AirPlan pl;
+  pl.is_ext.assign(n, 0);
+  pl.slot.assign(n, kAirNoSlot);
+  pl.last_use.resize(n);
+  std::vector<uint64_t> deg(n, 0);
+  std::vector<uint8_t> is_assert(n, 0);
+  uint64_t max_deg = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const p3r_air_insn& in = prog[i];
+    pl.last_use[i] = (uint32_t)i;
+    if (!air_op_known(in.op)) fail(P3R_EINVAL, "instruction %zu: unknown op %u", i, in.op);
+    const int n_ops = air_op_operands(in.op);
+    const uint32_t ops[2] = {in.a, in.b};
+    for (int k = 0; k < n_ops; ++k) {
+      if (ops[k] >= i) fail(P3R_EINVAL, "instruction %zu: operand %u is not an earlier value", i, ops[k]);
+      if (is_assert[ops[k]]) fail(P3R_EINVAL, "instruction %zu: operand %u is an ASSERT_ZERO, which has no value", i, ops[k]);
+      pl.last_use[ops[k]] = (uint32_t)i;
+    }
+    switch (in.op) {
+      case P3R_AIR_CONST:
+        if (in.a >= p) fail(P3R_EINVAL, "instruction %zu: non-canonical constant %u", i, in.a);
+        break;
+      case P3R_AIR_PUBLIC:
+        if (n_public != kAirUnknownCount && in.a >= n_public) fail(P3R_EINVAL, "instruction %zu: public value %u of %zu", i, in.a, n_public);
+        break;
+      case P3R_AIR_CHALLENGE:
+        if (n_challenges != kAirUnknownCount && in.a >= n_challenges) fail(P3R_EINVAL, "instruction %zu: challenge %u of %zu", i, in.a, n_challenges);
+        pl.is_ext[i] = 1;
+        break;
+      case P3R_AIR_LOCAL: case P3R_AIR_NEXT: case P3R_AIR_LOCAL_EXT: case P3R_AIR_NEXT_EXT: {
+        const bool e = in.op == P3R_AIR_LOCAL_EXT || in.op == P3R_AIR_NEXT_EXT;
+        if (in.a >= n_mats) fail(P3R_EINVAL, "instruction %zu: matrix %u of %zu", i, in.a, n_mats);
+        if ((uint64_t)in.b + (e ? (uint64_t)dc : 1) > widths[in.a])
+          fail(P3R_EINVAL, "instruction %zu: column%s %u%s of matrix %u, which has %zu", i, e ? "s" : "", in.b, e ? " .. + DC" : "", in.a, widths[in.a]);
+        pl.is_ext[i] = e;
+        deg[i] = 1;
+        break;
+      }
+      case P3R_AIR_IS_FIRST_ROW: case P3R_AIR_IS_LAST_ROW:
+        pl.uses_x = pl.uses_inv = true;
+        deg[i] = 1;
+        break;
+      case P3R_AIR_IS_TRANSITION:
+        pl.uses_x = true;
+        break;
+      case P3R_AIR_ADD: case P3R_AIR_SUB:
+        pl.is_ext[i] = pl.is_ext[in.a] | pl.is_ext[in.b];
+        deg[i] = std::max(deg[in.a], deg[in.b]);
+        break;
+      case P3R_AIR_MUL:
+        pl.is_ext[i] = pl.is_ext[in.a] | pl.is_ext[in.b];
+        deg[i] = std::min(deg[in.a] + deg[in.b], kDegCap);
+        break;
+      case P3R_AIR_NEG:
+        pl.is_ext[i] = pl.is_ext[in.a];
+        deg[i] = deg[in.a];
+        break;
+      case P3R_AIR_ASSERT_ZERO:
+        is_assert[i] = 1;
+        ++pl.info.n_constraints;
+        max_deg = std::max(max_deg, deg[in.a]);
+        break;
+    }
+  }
+  if (pl.info.n_constraints == 0) fail(P3R_EINVAL, "the program has no ASSERT_ZERO");
+  pl.info.max_degree = (uint32_t)std::min<uint64_t>(max_deg, 0xffffffffu);
+  pl.info.log_quotient_degree = air_log_quotient_degree(max_deg);
+
+  // liveness and slots: a linear scan over last uses, one free list per kind, lowest slot first
+  using Heap = std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>>;
+  Heap free_slots[2];
+  uint32_t* region[2] = {&pl.n_base_slots, &pl.n_ext_slots};
+  uint32_t live = 0, peak = 0;
+  auto release = [&](uint32_t v) {
+    free_slots[pl.is_ext[v]].push(pl.slot[v]);
+    --live;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    const p3r_air_insn& in = prog[i];
+    const int n_ops = air_op_operands(in.op);
+    if (n_ops >= 1 && pl.last_use[in.a] == i) release(in.a);
+    if (n_ops == 2 && in.b != in.a && pl.last_use[in.b] == i) release(in.b);
+    if (is_assert[i]) continue;
+    const int kind = pl.is_ext[i];
+    if (free_slots[kind].empty()) {
+      pl.slot[i] = (*region[kind])++;
+    } else {
+      pl.slot[i] = free_slots[kind].top();
+      free_slots[kind].pop();
+    }
+    peak = std::max(peak, ++live);
+    if (pl.last_use[i] == i) release((uint32_t)i);   // never read: its slot is free again at once
+  }
+  pl.info.peak_live = peak;
+  if (peak > max_live)
+    fail(P3R_EUNSUPPORTED, "the program keeps %u values alive at once; P3R_AIR_MAX_LIVE is %u", peak, max_live);
+  return pl;
+}
+
+// ---- the interpreter's instruction stream
+enum AirDevOp : uint32_t {
+  AIR_D_CONST,       // dst <- a (a Montgomery word)
+  AIR_D_CONST_EXT,   // dst <- ext_consts[a .. a + DC)
+  AIR_D_LOAD,        // dst <- column a at the current (b = 0) / next (b = 1) row
+  AIR_D_LOAD_EXT,    // dst <- columns a .. a + DC
+  AIR_D_FIRST, AIR_D_LAST, AIR_D_TRANS,
+  AIR_D_ADD_BB, AIR_D_ADD_EE, AIR_D_ADD_EB,                 // _EB: a extension, b base
+  AIR_D_SUB_BB, AIR_D_SUB_EE, AIR_D_SUB_EB, AIR_D_SUB_BE,   // _BE: a base, b extension
+  AIR_D_MUL_BB, AIR_D_MUL_EE, AIR_D_MUL_EB,
+  AIR_D_NEG_B, AIR_D_NEG_E,
+  AIR_D_ASSERT_B, AIR_D_ASSERT_E                            // acc <- acc * alpha + a
+};
+struct AirDevInsn {
+  uint32_t op, dst, a, b;   // dst and value operands: LDS words of a lane
+};
+struct AirCompiled {
+  std::vector<AirDevInsn> insns;
+  std::vector<uint32_t> ext_consts;   // Montgomery, DC words per challenge the program reads
+};
+
+// publics / challenges: canonical and already checked for range.
+template <class PP>
+inline AirCompiled air_compile(const AirPlan& pl, const p3r_air_insn* prog, size_t n, const size_t* widths, size_t n_mats, int dc,
+                               const uint32_t* publics, const uint32_t* challenges) {
+  using F = Fp<PP>;
+  std::vector<uint32_t> col0(n_mats + 1, 0);   // first flat column of a matrix
+  for (size_t m = 0; m < n_mats; ++m) col0[m + 1] = col0[m] + (uint32_t)widths[m];
+  AirCompiled out;
+  out.insns.reserve(n);
+  for (size_t i = 0; i < n; ++i) {
+    const p3r_air_insn& in = prog[i];
+    AirDevInsn d{};
+    d.dst = in.op == P3R_AIR_ASSERT_ZERO ? 0 : pl.word_of(i, dc);
+    const int n_ops = air_op_operands(in.op);
+    const bool ea = n_ops >= 1 && pl.is_ext[in.a], eb = n_ops == 2 && pl.is_ext[in.b];
+    uint32_t wa = n_ops >= 1 ? pl.word_of(in.a, dc) : 0, wb = n_ops == 2 ? pl.word_of(in.b, dc) : 0;
+    switch (in.op) {
+      case P3R_AIR_CONST: d.op = AIR_D_CONST; wa = F::from_canonical(in.a).v; break;
+      case P3R_AIR_PUBLIC: d.op = AIR_D_CONST; wa = F::from_canonical(publics[in.a]).v; break;
+      case P3R_AIR_CHALLENGE:
+        d.op = AIR_D_CONST_EXT;
+        wa = (uint32_t)out.ext_consts.size();
+        for (int k = 0; k < dc; ++k) out.ext_consts.push_back(F::from_canonical(challenges[(size_t)in.a * dc + k]).v);
+        break;
+      case P3R_AIR_LOCAL: case P3R_AIR_NEXT: d.op = AIR_D_LOAD; wa = col0[in.a] + in.b; wb = in.op == P3R_AIR_NEXT; break;
+      case P3R_AIR_LOCAL_EXT: case P3R_AIR_NEXT_EXT: d.op = AIR_D_LOAD_EXT; wa = col0[in.a] + in.b; wb = in.op == P3R_AIR_NEXT_EXT; break;
+      case P3R_AIR_IS_FIRST_ROW: d.op = AIR_D_FIRST; break;
+      case P3R_AIR_IS_LAST_ROW: d.op = AIR_D_LAST; break;
+      case P3R_AIR_IS_TRANSITION: d.op = AIR_D_TRANS; break;
+      case P3R_AIR_ADD:
+        d.op = ea && eb ? AIR_D_ADD_EE : ea || eb ? AIR_D_ADD_EB : AIR_D_ADD_BB;
+        if (!ea && eb) std::swap(wa, wb);
+        break;
+      case P3R_AIR_SUB: d.op = ea && eb ? AIR_D_SUB_EE : ea ? AIR_D_SUB_EB : eb ? AIR_D_SUB_BE : AIR_D_SUB_BB; break;
+      case P3R_AIR_MUL:
+        d.op = ea && eb ? AIR_D_MUL_EE : ea || eb ? AIR_D_MUL_EB : AIR_D_MUL_BB;
+        if (!ea && eb) std::swap(wa, wb);
+        break;
+      case P3R_AIR_NEG: d.op = ea ? AIR_D_NEG_E : AIR_D_NEG_B; break;
+      case P3R_AIR_ASSERT_ZERO: d.op = ea ? AIR_D_ASSERT_E : AIR_D_ASSERT_B; break;
+    }
+    d.a = wa;
+    d.b = wb;
+    out.insns.push_back(d);
+  }
+  return out;
+}
+
+// ---- the quotient domain: N = h * 2^q points shift * w_N^i; chunk c = i mod 2^q is the coset (shift * w_N^c) * <w_h>,
+// on which x^h - 1 is the constant shift^h * w_{2^q}^c - 1 (QuotientArgs::zh / zh_inv of the prover's own kernel).
+struct AirDomain {
+  uint32_t shift, w_n, g_inv;                       // Montgomery: the shift, w_N, w_h^-1
+  uint32_t zh[1 << kAirMaxLogChunks], zh_inv[1 << kAirMaxLogChunks];
+};
+template <class PP>
+inline AirDomain air_domain(uint32_t shift_word, int log_h, int log_q) {
+  using F = Fp<PP>;
+  if (shift_word >= PP::P) fail(P3R_EINVAL, "coset shift must be a canonical element (0: the field's generator)");
+  if (log_q > kAirMaxLogChunks) fail(P3R_EUNSUPPORTED, "log_quotient_degree > %d is not supported", kAirMaxLogChunks);
+  if (log_h + log_q > PP::TWO_ADICITY) fail(P3R_EINVAL, "a quotient domain of 2^%d points exceeds the field's two-adicity (%d)", log_h + log_q, PP::TWO_ADICITY);
+  const F shift = shift_word ? F::from_canonical(shift_word) : F::generator();
+  AirDomain d{};
+  d.shift = shift.v;
+  d.w_n = F::two_adic_generator(log_h + log_q).v;
+  d.g_inv = F::two_adic_generator(log_h).inv().v;
+  const F shift_h = shift.pow(uint64_t(1) << log_h), w_c = F::two_adic_generator(log_q);
+  for (int c = 0; c < (1 << log_q); ++c) {
+    const F zh = shift_h * w_c.pow(c) - F::one();
+    if (zh.v == 0)
+      fail(P3R_EINVAL, "x^h - 1 has a zero in the quotient domain: shift^h is a 2^%d-th root of unity (chunk %d)", log_q, c);
+    d.zh[c] = zh.v;
+    d.zh_inv[c] = zh.inv().v;
+  }
+  return d;
+}
+
+}  // namespace p3r

@@ -5,6 +5,7 @@
 #include "kernels_stark.hip.h"
 #include "kernels_coop.hip.h"
 #include "tu_api.h"
+#include "air_program.h"
 #include "profile.h"
 #include "run_schedule.h"
 #include "prep_device.h"
@@ -838,6 +839,37 @@ int p3r_fri_final_poly_dmat(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_fina
 int p3r_fri_log_arity(const p3r_ctx* ctx, size_t phase, int log_cur, int log_final, int log_next_input) {
   if (!ctx) return -1;
   return fri_log_arity(ctx->fri_log_arities, phase, (int)ctx->cfg.max_log_arity, log_cur, log_final, log_next_input);
+}
+
+// The caller's AIR as a constraint program: air_program.h (the host half), tu_air.hip (the launch)
+int p3r_air_program_info(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
+                         p3r_air_info* out) {
+  return guard(nullptr, [&] {
+    if (!cfg || !out) fail(P3R_EINVAL, "NULL argument");
+    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
+    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
+      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
+    const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
+    *out = air_plan(prog, n_insns, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p, kAirUnknownCount, kAirUnknownCount,
+                    P3R_AIR_MAX_LIVE).info;
+  });
+}
+int p3r_quotient_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,
+                              uint32_t added_bits, uint32_t shift, uint32_t log_quotient_degree, const uint32_t* public_values,
+                              size_t n_public, const uint32_t* challenges, size_t n_challenges, const uint32_t* alpha, p3r_dmat** outs) {
+  return guard(ctx, [&] {
+    if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
+    if (!outs) fail(P3R_EINVAL, "outs is NULL");
+    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
+    std::vector<const p3r_dmat*> ms(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
+      ms[i] = mats[i];
+    }
+    auto res = P3R_FIELD_CALL(ctx, quotient_program, ctx, prog, n_insns, ms, added_bits, shift, log_quotient_degree, public_values,
+                              n_public, challenges, n_challenges, alpha);
+    for (size_t i = 0; i < res.size(); ++i) outs[i] = res[i].release();
+  });
 }
 
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,

@@ -6,7 +6,8 @@
 // opening seam: it includes open_impl.hip.h, as p3r_core.hip does, for the planner OpenPlan and instantiates the K9
 // kernels of kernels_open.hip.h with the seam's entry point), tu_fri.hip (the reduced openings and the fold at the public
 // FRI seam and the commit-phase leaf view: kernels_fri_points.hip.h, and its own instances of k_fri_inv_points, k_fri_vsum
-// and k_fri_fold),
+// and k_fri_fold), tu_air.hip (the constraint-program seam: the interpreter k_quotient_program of kernels_air.hip.h over the
+// plan and instruction stream of air_program.h),
 // prep_device.hip.
 // Kernels never call across units; only these host entry points do.
 #pragma once
@@ -104,6 +105,17 @@ std::unique_ptr<p3r_dmat> fri_fold(p3r_ctx* ctx, const p3r_dmat* in, uint32_t lo
 // = the flattened elements r << log_arity .. (r + 1) << log_arity.  Refuses what fri_fold refuses; only enqueues.
 template <class PP>
 std::unique_ptr<p3r_dmat> fri_leaf_view(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_arity);
+
+// quotient_values + split_evals for a caller's AIR (tu_air.hip): the p3r_air_insn program `prog` evaluated on the quotient
+// domain of 2^log_quotient_degree cosets of the trace domain, read from the first rows of the bit-reversed LDEs `mats` (one
+// height, blow-up 2^added_bits, over shift * <w>; shift 0 = the field's generator).  publics / challenges / alpha: canonical
+// host words.  Returns the 2^log_quotient_degree chunks, each h x DC in natural order.  Everything that is refused is
+// refused before anything is allocated or launched (include/p3r.h lists it); only enqueues.
+template <class PP>
+std::vector<std::unique_ptr<p3r_dmat>> quotient_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns,
+                                                        const std::vector<const p3r_dmat*>& mats, uint32_t added_bits, uint32_t shift,
+                                                        uint32_t log_quotient_degree, const uint32_t* publics, size_t n_public,
+                                                        const uint32_t* challenges, size_t n_challenges, const uint32_t* alpha);
 
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>

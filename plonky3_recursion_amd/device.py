@@ -12,6 +12,8 @@ Names follow the reference's traits where one exists:
   Challenger            DuplexChallenger<F, Perm16, 16, 8> (circuit-prover/src/config.rs), with the proof-of-work search
   fri_leaf_view_device  the matrix ExtensionMmcs::commit_matrix commits in a FRI commit phase
   prove_fri             p3_fri::prover::prove_fri (commit phase, final polynomial, query openings) from the calls above
+  AirBuilder            p3_uni_stark::SymbolicAirBuilder: an Air::eval recorded as a p3r_air_insn program
+  quotient_device       p3_uni_stark::prove's quotient_values + split_evals for that program, on resident LDEs
   permute_batch         CryptographicPermutation<[F;16]>::permute over a batch
   generate_trace_rows   Poseidon2CircuitAir::generate_trace_rows (poseidon2-circuit-air/src/air.rs:280)
 """
@@ -168,6 +170,117 @@ def mmcs_verify(cfg, cap, dims, index, opened_values, proof, salts=None):
         rc = lib.p3r_mmcs_verify(C.byref(cfg), cp, n, hs, ws, int(index), op, pp, pf.shape[0], err, len(err))
     if rc != 0:
         raise P3rError(rc, err.value.decode())
+
+
+class AirValue:
+    """A value of an AirBuilder program: the id of the instruction that defines it.  + - * and unary - record
+    instructions; a Python int operand becomes a constant (reduced into the field)."""
+
+    def __init__(self, builder, idx):
+        self.builder, self.idx = builder, idx
+
+    def _lift(self, o):
+        if isinstance(o, AirValue):
+            if o.builder is not self.builder:
+                raise P3rError(-1, "a value of another AirBuilder")
+            return o
+        return self.builder.const(int(o) % self.builder.p)
+
+    def __add__(self, o):
+        return self.builder._emit(_lib.P3R_AIR_ADD, self.idx, self._lift(o).idx)
+
+    def __radd__(self, o):
+        return self._lift(o) + self
+
+    def __sub__(self, o):
+        return self.builder._emit(_lib.P3R_AIR_SUB, self.idx, self._lift(o).idx)
+
+    def __rsub__(self, o):
+        return self._lift(o) - self
+
+    def __mul__(self, o):
+        return self.builder._emit(_lib.P3R_AIR_MUL, self.idx, self._lift(o).idx)
+
+    def __rmul__(self, o):
+        return self._lift(o) * self
+
+    def __neg__(self):
+        return self.builder._emit(_lib.P3R_AIR_NEG, self.idx, 0)
+
+
+class AirBuilder:
+    """The SymbolicAirBuilder of the seam: an AIR's `eval` written against this object records the straight-line
+    p3r_air_insn program Context.quotient_device evaluates (include/p3r.h has the format and the semantics).  Values are
+    base-field or challenge-field elements; the type follows from the operands.  Nothing is checked here: the library
+    validates a program (air_program_info, quotient_device)."""
+
+    def __init__(self, field="koala-bear"):
+        self.field, self.p, self.insns = field, MODULUS[field], []
+
+    def _emit(self, op, a=0, b=0):
+        self.insns.append((int(op), int(a), int(b)))
+        return AirValue(self, len(self.insns) - 1)
+
+    def const(self, word):
+        return self._emit(_lib.P3R_AIR_CONST, word)
+
+    def public(self, index):
+        return self._emit(_lib.P3R_AIR_PUBLIC, index)
+
+    def challenge(self, index):
+        return self._emit(_lib.P3R_AIR_CHALLENGE, index)
+
+    def local(self, matrix, column):
+        return self._emit(_lib.P3R_AIR_LOCAL, matrix, column)
+
+    def next(self, matrix, column):
+        return self._emit(_lib.P3R_AIR_NEXT, matrix, column)
+
+    def local_ext(self, matrix, column):
+        """The extension element stored flattened in DC consecutive columns from `column` on."""
+        return self._emit(_lib.P3R_AIR_LOCAL_EXT, matrix, column)
+
+    def next_ext(self, matrix, column):
+        return self._emit(_lib.P3R_AIR_NEXT_EXT, matrix, column)
+
+    def is_first_row(self):
+        return self._emit(_lib.P3R_AIR_IS_FIRST_ROW)
+
+    def is_last_row(self):
+        return self._emit(_lib.P3R_AIR_IS_LAST_ROW)
+
+    def is_transition(self):
+        return self._emit(_lib.P3R_AIR_IS_TRANSITION)
+
+    def assert_zero(self, value):
+        self._emit(_lib.P3R_AIR_ASSERT_ZERO, value.idx)
+
+    def program(self):
+        """The instructions as an (n, 3) uint32 array of (op, a, b)."""
+        return np.array(self.insns, dtype=np.uint32).reshape(-1, 3)
+
+
+def _air_insns(program):
+    prog = program.program() if isinstance(program, AirBuilder) else np.ascontiguousarray(program, dtype=np.uint32).reshape(-1, 3)
+    arr = (_lib.P3rAirInsn * max(1, len(prog)))()
+    for i, (op, a, b) in enumerate(prog.tolist()):
+        arr[i].op, arr[i].a, arr[i].b = op, a, b
+    return arr, len(prog)
+
+
+def air_program_info(cfg, program, widths):
+    """p3r_air_program_info on the host (no GPU): validates `program` (an AirBuilder or an (n, 3) array of (op, a, b))
+    against the matrix `widths` under the field and challenge degree of the p3r_config `cfg`; returns a dict of
+    n_constraints, max_degree, log_quotient_degree (the smallest the program may be evaluated with) and peak_live.
+    Raises P3rError with the reason when the program is refused."""
+    lib = _lib.load()
+    arr, n = _air_insns(program)
+    ws = (C.c_size_t * max(1, len(widths)))(*[int(w) for w in widths])
+    info = _lib.P3rAirInfo()
+    rc = lib.p3r_air_program_info(C.byref(cfg), arr, n, ws, len(widths), C.byref(info))
+    if rc != 0:
+        raise P3rError(rc, lib.p3r_last_error(None).decode())
+    return {k: int(getattr(info, k)) for k, _ in _lib.P3rAirInfo._fields_}
 
 
 class Context:
@@ -441,6 +554,31 @@ class Context:
         out = C.c_void_p()
         self.check(self.lib.p3r_fri_fold_dmat(self.h, dmat.h, log_arity, bp, None if roll_in is None else roll_in.h, C.byref(out)))
         return DeviceMatrix(self, self.ptr(out.value))
+
+    # ---- the caller's AIR: quotient_values + split_evals for a constraint program
+    def air_program_info(self, program, widths):
+        """air_program_info under this context's field and challenge degree."""
+        return air_program_info(self.cfg, program, widths)
+
+    def quotient_device(self, program, dmats, added_bits, log_quotient_degree, alpha, public_values=(), challenges=(), shift=None):
+        """The quotient chunks of the AIR `program` (an AirBuilder or an (n, 3) array of (op, a, b)) over the committed LDEs
+        `dmats` - one height, blow-up 2^added_bits, bit-reversed rows over shift * <w> as coset_lde_batch_device returns
+        them (`shift` None: the field's generator); only their first h << log_quotient_degree rows are read.
+        `public_values`: canonical words; `challenges`: (n, DC) canonical words; `alpha`: the DC words of the constraint
+        folding challenge.  Returns 2^log_quotient_degree new (h, DC) DeviceMatrix: row r of chunk c is the quotient at
+        (shift * w_N^c) * w_h^r - what split_evals returns; coset_lde_batch_device(chunk, added_bits, G / (shift * w_N^c))
+        extends it onto the commit coset.  The inputs are left as they are."""
+        dc = self.challenge_degree
+        arr, n = _air_insns(program)
+        mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+        pv, pvp = _u32(np.asarray(public_values, dtype=np.uint32).reshape(-1))
+        ch, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
+        al, alp = _u32(np.asarray(alpha, dtype=np.uint32).reshape(dc))
+        n_out = 1 << min(int(log_quotient_degree), 4)   # a larger log_quotient_degree is refused by the library
+        outs = (C.c_void_p * n_out)()
+        self.check(self.lib.p3r_quotient_program_dmat(self.h, arr, n, mats, len(dmats), int(added_bits), 0 if shift is None else int(shift),
+                                                      int(log_quotient_degree), pvp, pv.size, chp, len(ch), alp, outs))
+        return [DeviceMatrix(self, self.ptr(h)) for h in outs]
 
     # ---- the rest of prove_fri: challenger, commit-phase leaf view, final polynomial, schedule, and their composition
     def challenger(self):
