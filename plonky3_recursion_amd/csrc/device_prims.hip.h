@@ -9,6 +9,11 @@
 //                   sum over the [digit][block] counts, then a scatter in which every wave walks its keys in order and
 //                   ranks the 64 keys of a step against each other with eight ballots (the lanes that share a digit:
 //                   AND of the eight bit votes), so equal digits keep their input order without a single atomic.
+// and the three idioms the pass composes from them:
+//   ranks_of        exclusive_sum plus the total at [n], written by a one-thread kernel.
+//   select_marked   ranks_of over a 0 / 1 array and, on request, the list of the marked indices.
+//   order_by_level  iota, sort_pairs, the first sorted position of every key and, on request, the exclusive sums of
+//                   per-item lengths in sorted order.
 #pragma once
 #include "context.h"
 
@@ -222,6 +227,78 @@ inline void sort_pairs(hipStream_t s, const uint32_t* keys_in, uint32_t* keys_ou
     hipLaunchKernelGGL(k_sort_scatter, dim3(n_blocks), dim3(kPB), 0, s, src_k, src_v, dst_k, dst_v, n, shift, mask, counts.p, n_blocks);
     src_k = dst_k;
     src_v = dst_v;
+  }
+  P3R_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------- the pass's idioms
+inline unsigned blocks_of(size_t n) { return (unsigned)((n + kPB - 1) / kPB); }
+
+// total = excl[n-1] + fn(n-1)
+template <class T, class Fn>
+__global__ void k_scan_total(Fn fn, size_t n, T* __restrict__ excl) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) excl[n] = n ? excl[n - 1] + fn(n - 1) : 0;
+}
+// Ranks of a predicate (or packed counters) over an index range: out[i] = fn(0) + .. + fn(i - 1) for i <= n, so the total
+// stands at out[n] - on the device, where a caller can read several totals back with one blocking copy.
+template <class T, class Fn>
+void ranks_of(hipStream_t s, Fn fn, size_t n, T* out /* n + 1 */) {
+  exclusive_sum<T>(s, fn, n, out);
+  hipLaunchKernelGGL((k_scan_total<T, Fn>), dim3(1), dim3(64), 0, s, fn, n, out);
+  P3R_HIP(hipGetLastError());
+}
+
+static __global__ void __launch_bounds__(kPB) k_compact_marked(const uint32_t* __restrict__ marks, const uint32_t* __restrict__ rank, size_t n,
+                                                                uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kPB + threadIdx.x;
+  if (i < n && marks[i]) out[rank[i]] = (uint32_t)i;
+}
+// Mark, rank, count, compact: marks[0 .. n) are 0 / 1; rank[i] = the marked items before i, the count at rank[n]; with
+// `list`, list[k] = index of the k-th marked item.  n = 0: nothing is launched and no buffer is touched.
+inline void select_marked(hipStream_t s, const uint32_t* marks, size_t n, uint32_t* rank /* n + 1 */, uint32_t* list = nullptr) {
+  if (!n) return;
+  ranks_of<uint32_t>(s, LoadU32{marks}, n, rank);
+  if (list) hipLaunchKernelGGL(k_compact_marked, dim3(blocks_of(n)), dim3(kPB), 0, s, marks, rank, n, list);
+  P3R_HIP(hipGetLastError());
+}
+// the same, and the count with one blocking read (n = 0: 0, without a read)
+inline size_t select_marked_count(hipStream_t s, const uint32_t* marks, size_t n, uint32_t* rank, uint32_t* list = nullptr) {
+  if (!n) return 0;
+  select_marked(s, marks, n, rank, list);
+  uint32_t count = 0;
+  P3R_HIP(copy_sync(s, &count, rank + n, 4, hipMemcpyDeviceToHost));
+  return count;
+}
+
+static __global__ void __launch_bounds__(kPB) k_gather_u32(const uint32_t* __restrict__ src, const uint32_t* __restrict__ idx, size_t n,
+                                                            uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kPB + threadIdx.x;
+  if (i < n) out[i] = src[idx[i]];
+}
+// first position of every key value in a SORTED key array (no atomics: 3 M increments of twenty counters serialise)
+static __global__ void __launch_bounds__(kPB) k_first_index(const uint32_t* __restrict__ sorted_keys, size_t n, uint32_t* __restrict__ first) {
+  const size_t i = (size_t)blockIdx.x * kPB + threadIdx.x;
+  if (i < n && (i == 0 || sorted_keys[i] != sorted_keys[i - 1])) first[sorted_keys[i]] = (uint32_t)i;
+}
+static __global__ void __launch_bounds__(kPB) k_iota(uint32_t* __restrict__ v, size_t n) {
+  const size_t i = (size_t)blockIdx.x * kPB + threadIdx.x;
+  if (i < n) v[i] = (uint32_t)i;
+}
+// Order segments by level: order[j] = the item at position j when the n items are sorted by keys[i] < 2^lbits, equal
+// keys in input order; first[key] = the first sorted position of every key that occurs (the caller presets the row, so a
+// key that does not occur keeps its 0xFFFFFFFF).  With `lens`: offs[j] = lens of the items before position j, summed.
+// n = 0: nothing is launched and no buffer is touched.
+inline void order_by_level(hipStream_t s, const uint32_t* keys, size_t n, int lbits, uint32_t* first, uint32_t* order,
+                           const uint32_t* lens = nullptr, uint32_t* offs = nullptr) {
+  if (!n) return;
+  DevBuf iota(n), sorted_keys(n);
+  hipLaunchKernelGGL(k_iota, dim3(blocks_of(n)), dim3(kPB), 0, s, iota.p, n);
+  sort_pairs(s, keys, sorted_keys.p, iota.p, order, n, lbits);
+  hipLaunchKernelGGL(k_first_index, dim3(blocks_of(n)), dim3(kPB), 0, s, sorted_keys.p, n, first);
+  if (lens) {
+    DevBuf len_sorted(n);
+    hipLaunchKernelGGL(k_gather_u32, dim3(blocks_of(n)), dim3(kPB), 0, s, lens, order, n, len_sorted.p);
+    exclusive_sum<uint32_t>(s, LoadU32{len_sorted.p}, n, offs);
   }
   P3R_HIP(hipGetLastError());
 }

@@ -8,6 +8,21 @@
 // walk becomes: atomicMin of the op index per witness (plus a short fixed-point loop for the two roles that
 // depend on another witness's state), then maps over the ops.  Ranks inside a table, offsets into the
 // packed arrays and the level-sorted order of the schedule are scans and one stable radix sort (device_prims.hip.h).
+//
+// Layout: the kernels, by the phase that launches them; then PrepWork, the working state of one preparation (inputs,
+// the device buffers and host counts that cross a phase boundary, grouped by the phase that produces them) with one
+// function per phase; then devprep_impl, the list of the phases under their prof_stage names:
+//   prep_upload            upload_and_validate
+//   prep_bus_roles         table_ranks_and_lists, first_touches (fixed-point loop), bus_roles
+//   prep_traces            traces: one function per table, alu_lane_schedule
+//   prep_schedule_static   schedule_static: schedule_lists (flags, compacted lists, Horner runs), p2_mode_lists, w32_links
+//   prep_schedule_levels   schedule_levels (fixed-point loop)
+//   prep_schedule_emit     witness_rewrites (the only host-side map work)
+//   prep_emit_light / _chains / _p2 / _rest    emit_light, emit_chains, emit_p2 + emit_p2w, emit_rest, level_offsets
+// A phase that can hand the circuit to the host path returns bool; `bad` is read back at three points (after validation,
+// before the level loop, after k_any_unset), each guarding the indices that later launches trust.  The recurring steps
+// are calls into device_prims.hip.h: ranks_of (ranks of a predicate over the ops, total at [n]), select_marked (mark,
+// rank, count, compact) and order_by_level (stable order of segments by level, first index per level, offsets).
 #include "prep_device.h"
 #include "profile.h"
 
@@ -164,21 +179,6 @@ struct FlagP2W {  // rows of the width-32 Poseidon2 table
   const uint32_t* ops;
   __device__ uint32_t operator()(size_t i) const { return ops[8 * i] == P3R_OP_POSEIDON2_W32_PERM ? 1u : 0u; }
 };
-
-template <class Fn>
-void scan_pairs(p3r_ctx* ctx, Fn fn, size_t n, DevBuf& out /* n + 1 u64: exclusive sums, total at [n] */) {
-  out.alloc(2 * (n + 1));
-  prims::exclusive_sum<uint64_t>(ctx->stream, fn, n, reinterpret_cast<uint64_t*>(out.p));   // the total: k_scan_total
-}
-// total = excl[n-1] + fn(n-1)
-template <class Fn>
-__global__ void k_scan_total(Fn fn, size_t n, uint64_t* __restrict__ excl) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) excl[n] = n ? excl[n - 1] + fn(n - 1) : 0;
-}
-
-void scan_u32(p3r_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n) {
-  prims::exclusive_sum<uint32_t>(ctx->stream, prims::LoadU32{in}, n, out);
-}
 
 // op -> its row in its table; the tables' op lists
 __global__ void __launch_bounds__(kB) k_table_lists(const uint32_t* __restrict__ ops, size_t n_ops, const uint64_t* __restrict__ s_cp,
@@ -760,14 +760,6 @@ __global__ void __launch_bounds__(kB) k_chain_link(const uint32_t* __restrict__ 
 
 struct FlagReady { const uint32_t* f; __device__ uint32_t operator()(size_t i) const { return (f[i] & OF_READY) ? 1u : 0u; } };
 struct FlagLight { const uint32_t* f; __device__ uint32_t operator()(size_t i) const { return (f[i] & OF_LIGHT) ? 1u : 0u; } };
-template <class Fn>
-void scan_flags(p3r_ctx* ctx, Fn fn, size_t n, uint32_t* out /* n + 1 */) {
-  prims::exclusive_sum<uint32_t>(ctx->stream, fn, n, out);   // the total: k_flags_total
-}
-template <class Fn>
-__global__ void k_flags_total(Fn fn, size_t n, uint32_t* __restrict__ excl) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) excl[n] = n ? excl[n - 1] + fn(n - 1) : 0;
-}
 
 // compact: members of the Horner scans (ready steps, op order), the light ops (op order)
 __global__ void __launch_bounds__(kB) k_compact_ops(const uint32_t* __restrict__ oflags, size_t n_ops, const uint32_t* __restrict__ ready_rank,
@@ -779,11 +771,6 @@ __global__ void __launch_bounds__(kB) k_compact_ops(const uint32_t* __restrict__
   const uint32_t f = oflags[i];
   if (f & OF_READY) { hmem[ready_rank[i]] = (uint32_t)i; run_start[ready_rank[i]] = !(f & OF_LINK); }
   if (f & OF_LIGHT) light_ops[light_rank[i]] = (uint32_t)i;
-}
-__global__ void __launch_bounds__(kB) k_compact_marked(const uint32_t* __restrict__ marks, const uint32_t* __restrict__ rank, size_t n,
-                                                       uint32_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * kB + threadIdx.x;
-  if (i < n && marks[i]) out[rank[i]] = (uint32_t)i;
 }
 
 // Poseidon2 rows: position of a row among the rows of its mode (sponge / Merkle), and the mode lists
@@ -1127,27 +1114,12 @@ __global__ void __launch_bounds__(kB) k_list_kind(const uint32_t* __restrict__ o
 }
 
 // ---- emission ----------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kB) k_gather_u32(const uint32_t* __restrict__ src, const uint32_t* __restrict__ idx, size_t n,
-                                                   uint32_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * kB + threadIdx.x;
-  if (i < n) out[i] = src[idx[i]];
-}
-// first position of every key value in a SORTED key array (no atomics: 3 M increments of twenty counters serialise)
-__global__ void __launch_bounds__(kB) k_first_index(const uint32_t* __restrict__ sorted_keys, size_t n, uint32_t* __restrict__ first) {
-  const size_t i = (size_t)blockIdx.x * kB + threadIdx.x;
-  if (i < n && (i == 0 || sorted_keys[i] != sorted_keys[i - 1])) first[sorted_keys[i]] = (uint32_t)i;
-}
 __global__ void __launch_bounds__(kB) k_max_u32(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * kB + threadIdx.x;
   uint32_t x = i < n ? v[i] : 0u;
   for (int d = 32; d; d >>= 1) x = max(x, __shfl_xor(x, d));
   if ((threadIdx.x & 63) == 0 && x) atomicMax(out, x);
 }
-__global__ void __launch_bounds__(kB) k_iota(uint32_t* __restrict__ v, size_t n) {
-  const size_t i = (size_t)blockIdx.x * kB + threadIdx.x;
-  if (i < n) v[i] = (uint32_t)i;
-}
-
 // the device ext array: constants (Montgomery), hint output lists (bit 31: compare instead of write), recompose inputs
 template <class PP>
 __global__ void __launch_bounds__(kB) k_emit_ext(const uint32_t* __restrict__ ops, size_t n_ops, const uint32_t* __restrict__ ext,
@@ -1330,144 +1302,238 @@ __global__ void __launch_bounds__(kB) k_set_zero_at(const uint32_t* __restrict__
   if (i < n) v[idx[i]] = 0;
 }
 
-void sort_by_key(p3r_ctx* ctx, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n, int bits) {
-  if (!n) return;
-  prims::sort_pairs(ctx->stream, keys_in, keys_out, vals_in, vals_out, n, bits);
-}
 inline int bits_for(uint32_t max_value) {
   int b = 1;
   while (b < 32 && (max_value >> b)) ++b;
   return b;
 }
 
+// ------------------------------------------------------------------------------------------------ the driver's helpers
 template <class T>
 std::vector<T> fetch(p3r_ctx* ctx, const void* dev, size_t n) {
   std::vector<T> v(n);
   if (n) P3R_HIP(copy_sync(ctx->stream, v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost));
   return v;
 }
+// one blocking read of a word the stream has written
+inline uint32_t fetch_u32(p3r_ctx* ctx, const uint32_t* dev) {
+  uint32_t v = 0;
+  P3R_HIP(copy_sync(ctx->stream, &v, dev, 4, hipMemcpyDeviceToHost));
+  return v;
+}
+// allocation size of a list that may be empty: a kernel argument is never a null pointer
+inline size_t at_least_one(size_t n) { return std::max<size_t>(n, 1); }
+// host words -> device buffer (at least one cell), on the stream
+inline void up(p3r_ctx* ctx, DevBuf& b, const uint32_t* src, size_t n) {
+  b.alloc(at_least_one(n));
+  if (n) P3R_HIP(hipMemcpyAsync(b.p, src, n * 4, hipMemcpyHostToDevice, ctx->stream));
+}
+template <class T>
+T* as(DevBuf& b) { return reinterpret_cast<T*>(b.p); }
 
 #define LAUNCH(kern, n, ...) \
   do { if ((n) > 0) hipLaunchKernelGGL(kern, dim3(nblk(n)), dim3(kB), 0, ctx->stream, __VA_ARGS__); } while (0)
 
+// ------------------------------------------------------------------------------------------------ the pass
+// The working state of one preparation: what the phases hand to one another, grouped by the phase that produces it.
+// A buffer that lives inside one phase is a local of that phase.  The phases run in the order they are declared in
+// (devprep_impl); one that returns bool can hand the circuit to the host path (false).
 template <class PP>
-bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
-  const size_t n_ops = d->n_ops;
-  const uint32_t nw = d->witness_count;
-  if (nw >= (1u << 31) || n_ops >= (size_t(1) << 28) || n_ops == 0 || nw == 0) return false;  // host path: limits, degenerate circuits
-  const uint32_t D = ctx->cfg.ext_degree;
-  if (D != 1 && D != 4 && D != 5) return false;   // (the runner computes in these degrees)
-  const Shape sh = shape_of(D);
-  hipStream_t s = ctx->stream;
-  prof_stage(ctx, "prep_upload");
-  // ---- the circuit crosses PCIe once
-  DevBuf ops(n_ops * 8), ext(std::max<size_t>(d->n_ext, 1));
-  P3R_HIP(hipMemcpyAsync(ops.p, d->ops, n_ops * 32, hipMemcpyHostToDevice, s));
-  if (d->n_ext) P3R_HIP(hipMemcpyAsync(ext.p, d->ext, d->n_ext * 4, hipMemcpyHostToDevice, s));
-  auto up = [&](DevBuf& b, const uint32_t* src, size_t n) {
-    b.alloc(std::max<size_t>(n, 1));
-    if (n) P3R_HIP(hipMemcpyAsync(b.p, src, n * 4, hipMemcpyHostToDevice, s));
-  };
-  up(R.d_public_rows, d->public_rows, d->n_public);
-  up(R.d_private_rows, d->private_input_rows, d->n_private);
-  R.n_public_rows = d->n_public;
-  R.n_private_rows = d->n_private;
-  for (size_t k = 0; k < 2 * d->n_rewrite; ++k)
-    if (d->witness_rewrite[k] >= nw) return false;
+struct PrepWork {
+  // ---- inputs
+  p3r_ctx* const ctx;
+  const p3r_circuit_desc* const d;
+  DevPrep& R;               // the result
+  RunSchedule& S;           // R.sched
+  const hipStream_t s;
+  const uint32_t D;         // extension degree of the circuit
+  const Shape sh;           // layout of its Poseidon2 ops
+  const uint32_t nw;        // witnesses
+  const size_t n_ops;
+  const size_t mh;          // minimum trace height
 
-  DevBuf bad(2), changed(1);
-  P3R_HIP(hipMemsetAsync(bad.p, 0, 8, s));
-  DevBuf wflags(nw), tdef(nw), stime(nw), reads(nw), wlevel(nw);
-  P3R_HIP(hipMemsetAsync(wflags.p, 0, (size_t)nw * 4, s));
-  P3R_HIP(hipMemsetAsync(reads.p, 0, (size_t)nw * 4, s));
-  P3R_HIP(hipMemsetAsync(wlevel.p, 0, (size_t)nw * 4, s));
-  P3R_HIP(hipMemsetAsync(tdef.p, 0xFF, (size_t)nw * 4, s));
-  P3R_HIP(hipMemsetAsync(stime.p, 0xFF, (size_t)nw * 4, s));
-  LAUNCH(k_validate<PP>, n_ops, ops.p, n_ops, ext.p, d->n_ext, nw, sh, bad.p);
-  LAUNCH(k_mark_rows, d->n_public, R.d_public_rows.p, d->n_public, nw, 0u, wflags.p, stime.p, bad.p);
-  LAUNCH(k_mark_rows, d->n_private, R.d_private_rows.p, d->n_private, nw, (uint32_t)WF_PRIVATE, wflags.p, stime.p, bad.p);
-  {
-    uint32_t b0 = 0;
-    P3R_HIP(copy_sync(s, &b0, bad.p, 4, hipMemcpyDeviceToHost));
-    if (b0) return false;  // from here on every index is in range
+  PrepWork(p3r_ctx* ctx_, const p3r_circuit_desc* d_, DevPrep& R_)
+      : ctx(ctx_), d(d_), R(R_), S(R_.sched), s(ctx_->stream), D(ctx_->cfg.ext_degree), sh(shape_of(D)), nw(d_->witness_count),
+        n_ops(d_->n_ops), mh(d_->min_trace_height) {}
+
+  // ---- prep_upload
+  DevBuf ops;       // the op list: eight words per op (Op)
+  DevBuf ext;       // the operand lists the ops point into
+  DevBuf bad;       // [0]: BAD_* bits, any set = the host path reports
+  DevBuf changed;   // [0]: a sweep of a fixed-point loop lowered / raised something
+  DevBuf wflags;    // per witness: WF_* bits
+  DevBuf tdef;      // per witness: time (op index + 1) of the op that defines it on the bus
+  DevBuf stime;     // per witness: time of the op that sets it at run time (0: an input; kUnset: nobody)
+  DevBuf reads;     // per witness: bus reads
+  DevBuf wlevel;    // per witness: schedule level at which it is set
+
+  // ---- prep_bus_roles
+  DevBuf s_cp;      // per op, u64: Const ops before it | Public ops before it << 32; totals at [n_ops] (all five)
+  DevBuf s_ap;      // per op, u64: ALU ops | width-16 Poseidon2 ops << 32
+  DevBuf s_re;      // per op, u64: plain Recompose ops | cells of the device ext array << 32
+  DevBuf s_rc;      // per op: `recompose/coeff` ops before it
+  DevBuf s_pw;      // per op: width-32 Poseidon2 ops before it
+  uint64_t* S_cp() { return as<uint64_t>(s_cp); }
+  uint64_t* S_ap() { return as<uint64_t>(s_ap); }
+  uint64_t* S_re() { return as<uint64_t>(s_re); }
+  size_t n_const = 0, n_public = 0, n_alu_ops = 0, n_p2 = 0, n_pw = 0;   // rows per table
+  size_t n_rec_plain = 0, n_rec_coeff = 0;   // Recompose ops of either kind: one trace array, the plain ones first
+  size_t n_dev_ext = 0;                      // cells of the device ext array
+  DevBuf const_ops, public_ops, alu_ops, p2_ops, rec_ops, rec_coeff_ops, pw_ops;   // row of a table -> its op
+  DevBuf roles;     // per ALU row: a_state | c_state << 8 | b_creator << 16 | out_creator << 24
+  size_t h_p2 = 0;  // padded height of the width-16 Poseidon2 table, 0 = absent
+
+  // ---- prep_schedule_static
+  DevBuf oflags;    // per op: RUN_* and OF_* bits
+  DevBuf olevel;    // per op: schedule level (light ops and Horner steps)
+  size_t n_members = 0, n_light = 0;   // Horner steps that can join a scan; light ops
+  DevBuf hmem;      // the Horner steps, op order
+  DevBuf light_ops; // the light ops, op order
+  size_t n_runs = 0;
+  DevBuf runs;      // first member of every Horner run (steps linked to the one before)
+  DevBuf chead;     // per member (+ 1): 1 = a chain starts here (the level loop raises them)
+  size_t n_p2_runs = 0, n_normal = 0;  // runs of chained permutations; sponge rows
+  DevBuf mlist;     // Poseidon2 rows by mode: sponge rows in order, then Merkle rows in order
+  DevBuf mpos;      // row -> its position in mlist
+  DevBuf p2_runs;   // mlist position that opens each run
+  DevBuf plevel;    // per mlist position: schedule level
+  DevBuf phead;     // per mlist position (+ 1): 1 = a segment starts here
+  size_t n_pw_sponge = 0;
+  DevBuf pw_sponge; // per width-32 row: 1 = sponge row
+  DevBuf pw_srank;  // its rank among the sponge rows (count at [n_pw])
+  DevBuf pw_slist;  // the sponge rows in order
+  DevBuf pw_prev;   // per width-32 row: the row whose state it continues, or kNoW
+  DevBuf pw_level;  // per width-32 row: schedule level
+  DevBuf pw_joined; // per width-32 row: 1 = runs in its predecessor's segment
+
+  // ---- emission
+  uint32_t max_level = 0;
+  size_t nl1 = 0;   // max_level + 2: cells of a histogram row
+  int lbits = 1;    // bits of the largest sort key, 2 * max_level + 1
+  DevBuf hist;      // first[key] per sorted array, kUnset = the key does not occur: three rows, the chains' twice as long
+  DevBuf histw;     // the same for the width-32 segments
+  uint32_t* first_light() { return hist.p; }            // light ops by level
+  uint32_t* first_seg() { return hist.p + nl1; }        // width-16 segments by level
+  uint32_t* first_chain() { return hist.p + 2 * nl1; }  // chains by 2 * level + (short ? 1 : 0)
+  size_t n_chains = 0, n_segs = 0, n_wsegs = 0;         // Horner chains, width-16 segments, width-32 segments
+  RunOp* light() { return as<RunOp>(R.d_light); }
+  RunOp* chain_ops() { return as<RunOp>(R.d_chain_ops); }
+  RunSchedule::ChainSeg* chains() { return as<RunSchedule::ChainSeg>(R.d_chains); }
+  RunSchedule::P2Seg* p2segs() { return as<RunSchedule::P2Seg>(R.d_p2segs); }
+  RunSchedule::P2Seg* p2wsegs() { return as<RunSchedule::P2Seg>(R.d_p2wsegs); }
+
+  bool any_bad() { return fetch_u32(ctx, bad.p) != 0; }
+
+  // ---- prep_upload: the circuit crosses PCIe once; what the host path must report is found here
+  bool upload_and_validate() {
+    ops.alloc(n_ops * 8);
+    ext.alloc(at_least_one(d->n_ext));
+    P3R_HIP(hipMemcpyAsync(ops.p, d->ops, n_ops * 32, hipMemcpyHostToDevice, s));
+    if (d->n_ext) P3R_HIP(hipMemcpyAsync(ext.p, d->ext, d->n_ext * 4, hipMemcpyHostToDevice, s));
+    up(ctx, R.d_public_rows, d->public_rows, d->n_public);
+    up(ctx, R.d_private_rows, d->private_input_rows, d->n_private);
+    R.n_public_rows = d->n_public;
+    R.n_private_rows = d->n_private;
+    for (size_t k = 0; k < 2 * d->n_rewrite; ++k)
+      if (d->witness_rewrite[k] >= nw) return false;
+
+    bad.alloc(2);
+    changed.alloc(1);
+    P3R_HIP(hipMemsetAsync(bad.p, 0, 8, s));
+    for (DevBuf* b : {&wflags, &tdef, &stime, &reads, &wlevel}) b->alloc(nw);
+    P3R_HIP(hipMemsetAsync(wflags.p, 0, (size_t)nw * 4, s));
+    P3R_HIP(hipMemsetAsync(reads.p, 0, (size_t)nw * 4, s));
+    P3R_HIP(hipMemsetAsync(wlevel.p, 0, (size_t)nw * 4, s));
+    P3R_HIP(hipMemsetAsync(tdef.p, 0xFF, (size_t)nw * 4, s));
+    P3R_HIP(hipMemsetAsync(stime.p, 0xFF, (size_t)nw * 4, s));
+    LAUNCH(k_validate<PP>, n_ops, ops.p, n_ops, ext.p, d->n_ext, nw, sh, bad.p);
+    LAUNCH(k_mark_rows, d->n_public, R.d_public_rows.p, d->n_public, nw, 0u, wflags.p, stime.p, bad.p);
+    LAUNCH(k_mark_rows, d->n_private, R.d_private_rows.p, d->n_private, nw, (uint32_t)WF_PRIVATE, wflags.p, stime.p, bad.p);
+    return !any_bad();  // from here on every index is in range
   }
-  prof_stage(ctx, "prep_bus_roles");
-  // ---- ranks: op -> row of its table, offsets into the device ext array
-  DevBuf s_cp, s_ap, s_re;
-  scan_pairs(ctx, PairConstPublic{ops.p}, n_ops, s_cp);
-  scan_pairs(ctx, PairAluP2{ops.p}, n_ops, s_ap);
-  scan_pairs(ctx, PairRecExt{ops.p, D}, n_ops, s_re);
-  DevBuf s_rc(n_ops + 1);   // rank among the `recompose/coeff` ops
-  scan_flags(ctx, FlagRecCoeff{ops.p}, n_ops, s_rc.p);
-  hipLaunchKernelGGL(k_flags_total<FlagRecCoeff>, dim3(1), dim3(64), 0, s, FlagRecCoeff{ops.p}, n_ops, s_rc.p);
-  uint64_t* S_cp = reinterpret_cast<uint64_t*>(s_cp.p);
-  uint64_t* S_ap = reinterpret_cast<uint64_t*>(s_ap.p);
-  uint64_t* S_re = reinterpret_cast<uint64_t*>(s_re.p);
-  hipLaunchKernelGGL(k_scan_total<PairConstPublic>, dim3(1), dim3(64), 0, s, PairConstPublic{ops.p}, n_ops, S_cp);
-  hipLaunchKernelGGL(k_scan_total<PairAluP2>, dim3(1), dim3(64), 0, s, PairAluP2{ops.p}, n_ops, S_ap);
-  hipLaunchKernelGGL(k_scan_total<PairRecExt>, dim3(1), dim3(64), 0, s, PairRecExt{ops.p, D}, n_ops, S_re);
-  DevBuf s_pw(n_ops + 1);   // rank among the width-32 Poseidon2 ops
-  scan_flags(ctx, FlagP2W{ops.p}, n_ops, s_pw.p);
-  hipLaunchKernelGGL(k_flags_total<FlagP2W>, dim3(1), dim3(64), 0, s, FlagP2W{ops.p}, n_ops, s_pw.p);
-  uint64_t tot[3];
-  uint32_t n_rec_coeff_u32 = 0, n_pw_u32 = 0;
-  P3R_HIP(hipMemcpyAsync(&n_pw_u32, s_pw.p + n_ops, 4, hipMemcpyDeviceToHost, s));
-  P3R_HIP(hipMemcpyAsync(&n_rec_coeff_u32, s_rc.p + n_ops, 4, hipMemcpyDeviceToHost, s));
-  P3R_HIP(hipMemcpyAsync(&tot[0], S_cp + n_ops, 8, hipMemcpyDeviceToHost, s));
-  P3R_HIP(hipMemcpyAsync(&tot[1], S_ap + n_ops, 8, hipMemcpyDeviceToHost, s));
-  P3R_HIP(copy_sync(s, &tot[2], S_re + n_ops, 8, hipMemcpyDeviceToHost));
-  const size_t n_const = (uint32_t)tot[0], n_public = tot[0] >> 32, n_alu_ops = (uint32_t)tot[1], n_p2 = tot[1] >> 32;
-  // plain / coefficient-kind Recompose ops; their trace rows share one array, the plain ones first
-  const size_t n_rec_plain = (uint32_t)tot[2], n_rec_coeff = n_rec_coeff_u32, n_dev_ext = tot[2] >> 32;
-  DevBuf const_ops(std::max<size_t>(n_const, 1)), public_ops(std::max<size_t>(n_public, 1)), alu_ops(std::max<size_t>(n_alu_ops, 1)),
-      p2_ops(std::max<size_t>(n_p2, 1)), rec_ops(std::max<size_t>(n_rec_plain, 1)), rec_coeff_ops(std::max<size_t>(n_rec_coeff, 1));
-  LAUNCH(k_table_lists, n_ops, ops.p, n_ops, S_cp, S_ap, S_re, const_ops.p, public_ops.p, alu_ops.p, p2_ops.p, rec_ops.p, s_rc.p,
-         rec_coeff_ops.p);
-  const size_t n_pw = n_pw_u32;
-  DevBuf pw_ops(std::max<size_t>(n_pw, 1));
-  if (n_pw) LAUNCH(k_list_kind, n_ops, ops.p, n_ops, (uint32_t)P3R_OP_POSEIDON2_W32_PERM, s_pw.p, pw_ops.p);
 
-  // ---- first touches
-  LAUNCH(k_mark_cp, n_ops, ops.p, n_ops, wflags.p);
-  LAUNCH(k_mark_hint, n_ops, ops.p, n_ops, ext.p, wflags.p);
-  LAUNCH(k_times, n_ops, ops.p, n_ops, ext.p, wflags.p, sh, tdef.p, stime.p);
-  for (int round = 0;; ++round) {
-    P3R_HIP(hipMemsetAsync(changed.p, 0, 4, s));
-    for (int k = 0; k < 4; ++k) LAUNCH(k_times_fix, n_ops, ops.p, n_ops, wflags.p, tdef.p, stime.p, changed.p);
-    uint32_t c = 0;
-    P3R_HIP(copy_sync(s, &c, changed.p, 4, hipMemcpyDeviceToHost));
-    if (!c) break;
-    if (round > (1 << 20)) fail(P3R_EINVAL, "circuit preparation did not converge");
+  // ---- prep_bus_roles (1): op -> row of its table, offsets into the device ext array, the tables' op lists
+  void table_ranks_and_lists() {
+    for (DevBuf* b : {&s_cp, &s_ap, &s_re}) b->alloc(2 * (n_ops + 1));
+    s_rc.alloc(n_ops + 1);
+    s_pw.alloc(n_ops + 1);
+    prims::ranks_of<uint64_t>(s, PairConstPublic{ops.p}, n_ops, S_cp());
+    prims::ranks_of<uint64_t>(s, PairAluP2{ops.p}, n_ops, S_ap());
+    prims::ranks_of<uint64_t>(s, PairRecExt{ops.p, D}, n_ops, S_re());
+    prims::ranks_of<uint32_t>(s, FlagRecCoeff{ops.p}, n_ops, s_rc.p);
+    prims::ranks_of<uint32_t>(s, FlagP2W{ops.p}, n_ops, s_pw.p);
+    uint64_t tot[3];
+    uint32_t n_rec_coeff_u32 = 0, n_pw_u32 = 0;
+    P3R_HIP(hipMemcpyAsync(&n_pw_u32, s_pw.p + n_ops, 4, hipMemcpyDeviceToHost, s));
+    P3R_HIP(hipMemcpyAsync(&n_rec_coeff_u32, s_rc.p + n_ops, 4, hipMemcpyDeviceToHost, s));
+    P3R_HIP(hipMemcpyAsync(&tot[0], S_cp() + n_ops, 8, hipMemcpyDeviceToHost, s));
+    P3R_HIP(hipMemcpyAsync(&tot[1], S_ap() + n_ops, 8, hipMemcpyDeviceToHost, s));
+    P3R_HIP(copy_sync(s, &tot[2], S_re() + n_ops, 8, hipMemcpyDeviceToHost));
+    n_const = (uint32_t)tot[0]; n_public = tot[0] >> 32; n_alu_ops = (uint32_t)tot[1]; n_p2 = tot[1] >> 32;
+    n_rec_plain = (uint32_t)tot[2]; n_rec_coeff = n_rec_coeff_u32; n_dev_ext = tot[2] >> 32;
+    n_pw = n_pw_u32;
+    const_ops.alloc(at_least_one(n_const));
+    public_ops.alloc(at_least_one(n_public));
+    alu_ops.alloc(at_least_one(n_alu_ops));
+    p2_ops.alloc(at_least_one(n_p2));
+    rec_ops.alloc(at_least_one(n_rec_plain));
+    rec_coeff_ops.alloc(at_least_one(n_rec_coeff));
+    LAUNCH(k_table_lists, n_ops, ops.p, n_ops, S_cp(), S_ap(), S_re(), const_ops.p, public_ops.p, alu_ops.p, p2_ops.p, rec_ops.p, s_rc.p,
+           rec_coeff_ops.p);
+    pw_ops.alloc(at_least_one(n_pw));
+    if (n_pw) LAUNCH(k_list_kind, n_ops, ops.p, n_ops, (uint32_t)P3R_OP_POSEIDON2_W32_PERM, s_pw.p, pw_ops.p);
   }
 
-  // ---- bus roles, read counts
-  DevBuf roles(std::max<size_t>(n_alu_ops, 1));
-  LAUNCH(k_roles, n_ops, ops.p, n_ops, ext.p, wflags.p, tdef.p, sh, S_ap, reads.p, roles.p);
-  const size_t mh = d->min_trace_height;
-  R.counts.n_const = n_const; R.counts.n_public = n_public; R.counts.n_alu = std::max<size_t>(n_alu_ops, 1);
-  R.counts.n_p2 = n_p2;
-  R.counts.n_p2w = n_pw;
-  // a table without rows is not proved: a circuit whose Recompose ops are all of the coefficient kind has ONE Recompose
-  // table, `recompose/coeff`, in the first slot (circuit_impl.hip.h::circuit_tables)
-  R.recompose_coeff = n_rec_plain == 0 && n_rec_coeff > 0;
-  R.counts.n_recompose = R.recompose_coeff ? n_rec_coeff : n_rec_plain;
-  R.counts.n_recompose_coeff = R.recompose_coeff ? 0 : n_rec_coeff;
-  R.public_lanes = n_public <= 1 ? 1 : d->public_lanes;
-  R.alu_lanes = R.counts.n_alu <= 1 ? 1 : d->alu_lanes;
-  const size_t h_p2 = n_p2 ? padded_h(n_p2, mh) : 0;
-  LAUNCH(k_acc_reads, n_p2, ops.p, ext.p, p2_ops.p, n_p2, h_p2, sh, reads.p);
-  LAUNCH(k_unclaimed, d->n_private, R.d_private_rows.p, d->n_private, tdef.p, bad.p);
+  // ---- prep_bus_roles (2): the first op that touches a witness in each role
+  void first_touches() {
+    LAUNCH(k_mark_cp, n_ops, ops.p, n_ops, wflags.p);
+    LAUNCH(k_mark_hint, n_ops, ops.p, n_ops, ext.p, wflags.p);
+    LAUNCH(k_times, n_ops, ops.p, n_ops, ext.p, wflags.p, sh, tdef.p, stime.p);
+    for (int round = 0;; ++round) {
+      P3R_HIP(hipMemsetAsync(changed.p, 0, 4, s));
+      for (int k = 0; k < 4; ++k) LAUNCH(k_times_fix, n_ops, ops.p, n_ops, wflags.p, tdef.p, stime.p, changed.p);
+      if (!fetch_u32(ctx, changed.p)) break;
+      if (round > (1 << 20)) fail(P3R_EINVAL, "circuit preparation did not converge");
+    }
+  }
 
-  prof_stage(ctx, "prep_traces");
-  // ---- preprocessed traces
-  const int lanes = (int)R.alu_lanes, k_max = (int)d->horner_packed_steps, rl = (int)d->recompose_lanes, pl = (int)R.public_lanes;
-  R.h[0] = padded_h(std::max<size_t>(n_const, 1), mh);
-  R.prep[0] = zero_mat(ctx, R.h[0], 2);
-  LAUNCH(k_prep_simple<PP>, n_const, ops.p, const_ops.p, n_const, 1, 0, reads.p, wflags.p, D, R.h[0], R.prep[0]->d);
-  R.h[1] = padded_h(std::max<size_t>((n_public + pl - 1) / pl, 1), mh);
-  R.prep[1] = zero_mat(ctx, R.h[1], 2 * (size_t)pl);
-  LAUNCH(k_prep_simple<PP>, n_public, ops.p, public_ops.p, n_public, pl, 0, reads.p, wflags.p, D, R.h[1], R.prep[1]->d);
-  if (n_p2) {
+  // ---- prep_bus_roles (3): bus roles and read counts; the tables' sizes
+  void bus_roles() {
+    roles.alloc(at_least_one(n_alu_ops));
+    LAUNCH(k_roles, n_ops, ops.p, n_ops, ext.p, wflags.p, tdef.p, sh, S_ap(), reads.p, roles.p);
+    R.counts.n_const = n_const; R.counts.n_public = n_public; R.counts.n_alu = at_least_one(n_alu_ops);
+    R.counts.n_p2 = n_p2;
+    R.counts.n_p2w = n_pw;
+    // a table without rows is not proved: a circuit whose Recompose ops are all of the coefficient kind has ONE Recompose
+    // table, `recompose/coeff`, in the first slot (circuit_impl.hip.h::circuit_tables)
+    R.recompose_coeff = n_rec_plain == 0 && n_rec_coeff > 0;
+    R.counts.n_recompose = R.recompose_coeff ? n_rec_coeff : n_rec_plain;
+    R.counts.n_recompose_coeff = R.recompose_coeff ? 0 : n_rec_coeff;
+    R.public_lanes = n_public <= 1 ? 1 : d->public_lanes;
+    R.alu_lanes = R.counts.n_alu <= 1 ? 1 : d->alu_lanes;
+    h_p2 = n_p2 ? padded_h(n_p2, mh) : 0;
+    LAUNCH(k_acc_reads, n_p2, ops.p, ext.p, p2_ops.p, n_p2, h_p2, sh, reads.p);
+    LAUNCH(k_unclaimed, d->n_private, R.d_private_rows.p, d->n_private, tdef.p, bad.p);
+  }
+
+  // ---- prep_traces: the preprocessed traces, table by table
+  void traces() {
+    trace_const_public();
+    if (n_p2) trace_p2();
+    if (n_pw) trace_p2w();
+    trace_recompose();
+    alu_lane_schedule();
+  }
+  void trace_const_public() {
+    const int pl = (int)R.public_lanes;
+    R.h[0] = padded_h(at_least_one(n_const), mh);
+    R.prep[0] = zero_mat(ctx, R.h[0], 2);
+    LAUNCH(k_prep_simple<PP>, n_const, ops.p, const_ops.p, n_const, 1, 0, reads.p, wflags.p, D, R.h[0], R.prep[0]->d);
+    R.h[1] = padded_h(at_least_one((n_public + pl - 1) / pl), mh);
+    R.prep[1] = zero_mat(ctx, R.h[1], 2 * (size_t)pl);
+    LAUNCH(k_prep_simple<PP>, n_public, ops.p, public_ops.p, n_public, pl, 0, reads.p, wflags.p, D, R.h[1], R.prep[1]->d);
+  }
+  void trace_p2() {
     R.h[3] = h_p2;
     if (D == 4) {
       R.prep[3] = zero_mat(ctx, h_p2, 24);
@@ -1477,37 +1543,38 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
       LAUNCH(k_prep_p2_d1<PP>, h_p2, ops.p, ext.p, p2_ops.p, n_p2, reads.p, wflags.p, D, h_p2, R.prep[3]->d);
     }
   }
-  if (n_pw) {
+  void trace_p2w() {
     R.h[6] = padded_h(n_pw, mh);
     R.prep[6] = zero_mat(ctx, R.h[6], kP2WPrepCols);
     LAUNCH(k_prep_p2w<PP>, R.h[6], ops.p, ext.p, pw_ops.p, n_pw, reads.p, wflags.p, R.h[6], R.prep[6]->d);
   }
-  if (n_rec_plain) {
-    R.h[4] = padded_h(std::max<size_t>((n_rec_plain + rl - 1) / rl, 1), mh);
-    R.prep[4] = zero_mat(ctx, R.h[4], 2 * (size_t)rl);
-    LAUNCH(k_prep_simple<PP>, n_rec_plain, ops.p, rec_ops.p, n_rec_plain, rl, 1, reads.p, wflags.p, D, R.h[4], R.prep[4]->d);
+  void trace_recompose() {
+    const int rl = (int)d->recompose_lanes;
+    if (n_rec_plain) {
+      R.h[4] = padded_h(at_least_one((n_rec_plain + rl - 1) / rl), mh);
+      R.prep[4] = zero_mat(ctx, R.h[4], 2 * (size_t)rl);
+      LAUNCH(k_prep_simple<PP>, n_rec_plain, ops.p, rec_ops.p, n_rec_plain, rl, 1, reads.p, wflags.p, D, R.h[4], R.prep[4]->d);
+    }
+    if (n_rec_coeff) {
+      const int slot = R.recompose_coeff ? 4 : 5;
+      R.h[slot] = padded_h(at_least_one((n_rec_coeff + rl - 1) / rl), mh);
+      R.prep[slot] = zero_mat(ctx, R.h[slot], (2 + 2 * (size_t)D) * rl);
+      LAUNCH(k_prep_rec_coeff<PP>, n_rec_coeff, ops.p, ext.p, rec_coeff_ops.p, n_rec_coeff, rl, reads.p, wflags.p, D, R.h[slot],
+             R.prep[slot]->d);
+    }
   }
-  if (n_rec_coeff) {
-    const int slot = R.recompose_coeff ? 4 : 5;
-    R.h[slot] = padded_h(std::max<size_t>((n_rec_coeff + rl - 1) / rl, 1), mh);
-    R.prep[slot] = zero_mat(ctx, R.h[slot], (2 + 2 * (size_t)D) * rl);
-    LAUNCH(k_prep_rec_coeff<PP>, n_rec_coeff, ops.p, ext.p, rec_coeff_ops.p, n_rec_coeff, rl, reads.p, wflags.p, D, R.h[slot],
-           R.prep[slot]->d);
-  }
-  {
-    // ALU lane schedule
+  // the ALU lane schedule and the trace it lays out
+  void alu_lane_schedule() {
+    const int lanes = (int)R.alu_lanes, k_max = (int)d->horner_packed_steps;
     const size_t n = n_alu_ops;
     size_t rows = 1, chain_rows = 0;
     bool any = false;
-    DevBuf nonchain(n + 2), chain_start(n + 2), heads(n + 2), nonchain_rank(n + 2), chain_rank(n + 2), heads_rank(n + 2);
+    DevBuf nonchain(n), chain_start(n), heads(n), nonchain_rank(n + 1), chain_rank(n + 1), heads_rank(n + 1);
     if (n) {
       LAUNCH(k_alu_marks, n, ops.p, alu_ops.p, n, k_max, nonchain.p, chain_start.p, heads.p);
-      P3R_HIP(hipMemsetAsync(nonchain.p + n, 0, 4, s));
-      P3R_HIP(hipMemsetAsync(chain_start.p + n, 0, 4, s));
-      P3R_HIP(hipMemsetAsync(heads.p + n, 0, 4, s));
-      scan_u32(ctx, nonchain.p, nonchain_rank.p, n + 1);
-      scan_u32(ctx, chain_start.p, chain_rank.p, n + 1);
-      scan_u32(ctx, heads.p, heads_rank.p, n + 1);
+      prims::select_marked(s, nonchain.p, n, nonchain_rank.p);
+      prims::select_marked(s, chain_start.p, n, chain_rank.p);
+      prims::select_marked(s, heads.p, n, heads_rank.p);
       uint32_t t3[3];
       P3R_HIP(hipMemcpyAsync(&t3[0], nonchain_rank.p + n, 4, hipMemcpyDeviceToHost, s));
       P3R_HIP(hipMemcpyAsync(&t3[1], chain_rank.p + n, 4, hipMemcpyDeviceToHost, s));
@@ -1519,7 +1586,7 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
         const size_t fill = chain_rows * (size_t)(lanes - 1);
         rows = chain_rows + (n_nc > fill ? (n_nc - fill + lanes - 1) / lanes : 0);
       } else {
-        rows = std::max<size_t>((n + lanes - 1) / lanes, 1);
+        rows = at_least_one((n + lanes - 1) / lanes);
       }
     }
     R.alu_rows = rows;
@@ -1527,7 +1594,7 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
     const int pw = lanes * 13 + 7 * (k_max - 1);
     R.prep[2] = zero_mat(ctx, R.h[2], (size_t)pw);
     R.alu_plan.alloc(rows * lanes * (sizeof(AluPlanEntry) / 4));
-    AluPlanEntry* plan = reinterpret_cast<AluPlanEntry*>(R.alu_plan.p);
+    AluPlanEntry* plan = as<AluPlanEntry>(R.alu_plan);
     LAUNCH(k_plan_init, rows * lanes, rows * lanes, plan);
     if (n == 0) {
       // the dummy row of an empty ALU table (common.rs:283-286): one op, zero cells
@@ -1543,100 +1610,87 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
     if (n) LAUNCH(k_prep_alu<PP>, rows * lanes, ops.p, alu_ops.p, roles.p, reads.p, plan, rows, lanes, k_max, D, R.h[2], R.prep[2]->d);
   }
 
-  prof_stage(ctx, "prep_schedule_static");
-  // ---- execution schedule -------------------------------------------------------------------------------------
-  RunSchedule& S = R.sched;
-  DevBuf oflags(n_ops), olevel(n_ops);
-  P3R_HIP(hipMemsetAsync(olevel.p, 0, n_ops * 4, s));
-  LAUNCH(k_sched_static, n_ops, ops.p, n_ops, ext.p, stime.p, sh, oflags.p, bad.p);
-  LAUNCH(k_chain_link, n_ops, ops.p, n_ops, oflags.p);
-  DevBuf ready_rank(n_ops + 1), light_rank(n_ops + 1);
-  scan_flags(ctx, FlagReady{oflags.p}, n_ops, ready_rank.p);
-  scan_flags(ctx, FlagLight{oflags.p}, n_ops, light_rank.p);
-  hipLaunchKernelGGL(k_flags_total<FlagReady>, dim3(1), dim3(64), 0, s, FlagReady{oflags.p}, n_ops, ready_rank.p);
-  hipLaunchKernelGGL(k_flags_total<FlagLight>, dim3(1), dim3(64), 0, s, FlagLight{oflags.p}, n_ops, light_rank.p);
-  // NonPrimitiveOpId -> row
-  {
-    DevBuf mx(1);
+  // ---- prep_schedule_static: what the level loop iterates over
+  bool schedule_static() {
+    schedule_lists();
+    p2_mode_lists();
+    w32_links();
+    return !any_bad();  // (k_op_ids, k_p2_lists and k_pw_links check what the level loop and the emission index with)
+  }
+  // static flags per op, NonPrimitiveOpId -> row, the compacted lists of Horner steps and light ops, the Horner runs
+  void schedule_lists() {
+    oflags.alloc(n_ops);
+    olevel.alloc(n_ops);
+    P3R_HIP(hipMemsetAsync(olevel.p, 0, n_ops * 4, s));
+    LAUNCH(k_sched_static, n_ops, ops.p, n_ops, ext.p, stime.p, sh, oflags.p, bad.p);
+    LAUNCH(k_chain_link, n_ops, ops.p, n_ops, oflags.p);
+    DevBuf ready_rank(n_ops + 1), light_rank(n_ops + 1), mx(1);
+    prims::ranks_of<uint32_t>(s, FlagReady{oflags.p}, n_ops, ready_rank.p);
+    prims::ranks_of<uint32_t>(s, FlagLight{oflags.p}, n_ops, light_rank.p);
     prims::reduce_max(s, MaxNpoId{ops.p}, n_ops, mx.p);
     uint32_t t3[3];
     P3R_HIP(hipMemcpyAsync(&t3[0], mx.p, 4, hipMemcpyDeviceToHost, s));
     P3R_HIP(hipMemcpyAsync(&t3[1], ready_rank.p + n_ops, 4, hipMemcpyDeviceToHost, s));
     P3R_HIP(copy_sync(s, &t3[2], light_rank.p + n_ops, 4, hipMemcpyDeviceToHost));
     R.n_op_ids = t3[0];
+    n_members = t3[1];
+    n_light = t3[2];
     S.n_alu_records = (uint32_t)n_alu_ops;
-    // (sizes of the compacted lists)
     S.light.clear();
     R.n_rewrite = 0;
-    const size_t n_members = t3[1], n_light = t3[2];
-    R.d_row_of_op_id.alloc(std::max<size_t>(R.n_op_ids, 1));
-    P3R_HIP(hipMemsetAsync(R.d_row_of_op_id.p, 0xFF, std::max<size_t>(R.n_op_ids, 1) * 4, s));
+    const size_t n_ids = at_least_one(R.n_op_ids);
+    R.d_row_of_op_id.alloc(n_ids);
+    P3R_HIP(hipMemsetAsync(R.d_row_of_op_id.p, 0xFF, n_ids * 4, s));
     LAUNCH(k_op_ids, n_p2, ops.p, p2_ops.p, n_p2, R.n_op_ids, R.d_row_of_op_id.p, bad.p);
     if (n_pw) {
-      R.d_roww_of_op_id.alloc(std::max<size_t>(R.n_op_ids, 1));
-      P3R_HIP(hipMemsetAsync(R.d_roww_of_op_id.p, 0xFF, std::max<size_t>(R.n_op_ids, 1) * 4, s));
+      R.d_roww_of_op_id.alloc(n_ids);
+      P3R_HIP(hipMemsetAsync(R.d_roww_of_op_id.p, 0xFF, n_ids * 4, s));
       LAUNCH(k_op_ids, n_pw, ops.p, pw_ops.p, n_pw, R.n_op_ids, R.d_roww_of_op_id.p, bad.p);
       LAUNCH(k_ids_cross, R.n_op_ids, R.d_row_of_op_id.p, R.d_roww_of_op_id.p, R.n_op_ids, bad.p);
     }
-
-    DevBuf hmem(std::max<size_t>(n_members, 1)), run_start(n_members + 2), light_ops(std::max<size_t>(n_light, 1));
+    hmem.alloc(at_least_one(n_members));
+    light_ops.alloc(at_least_one(n_light));
+    DevBuf run_start(at_least_one(n_members)), run_rank(n_members + 1);   // per member: 1 = no link to the member before
     LAUNCH(k_compact_ops, n_ops, oflags.p, n_ops, ready_rank.p, light_rank.p, hmem.p, run_start.p, light_ops.p);
     // Horner runs
-    DevBuf run_rank(n_members + 2), runs(std::max<size_t>(n_members, 1)), chead(std::max<size_t>(n_members, 1) + 1);
-    size_t n_runs = 0;
-    if (n_members) {
-      P3R_HIP(hipMemsetAsync(run_start.p + n_members, 0, 4, s));
-      scan_u32(ctx, run_start.p, run_rank.p, n_members + 1);
-      uint32_t v = 0;
-      P3R_HIP(copy_sync(s, &v, run_rank.p + n_members, 4, hipMemcpyDeviceToHost));
-      n_runs = v;
-      LAUNCH(k_compact_marked, n_members, run_start.p, run_rank.p, n_members, runs.p);
-      P3R_HIP(hipMemsetAsync(chead.p, 0, (n_members + 1) * 4, s));
-    }
-    // Poseidon2 mode lists and runs
-    DevBuf is_merkle(n_p2 + 2), merkle_rank(n_p2 + 2), mlist(std::max<size_t>(n_p2, 1)), mpos(std::max<size_t>(n_p2, 1)),
-        p2_run_start(n_p2 + 2), p2_run_rank(n_p2 + 2), p2_runs(std::max<size_t>(n_p2, 1)), plevel(std::max<size_t>(n_p2, 1)),
-        phead(n_p2 + 2);
-    size_t n_p2_runs = 0, n_normal = 0;
-    if (n_p2) {
-      LAUNCH(k_p2_modes, n_p2, ops.p, p2_ops.p, n_p2, is_merkle.p);
-      P3R_HIP(hipMemsetAsync(is_merkle.p + n_p2, 0, 4, s));
-      scan_u32(ctx, is_merkle.p, merkle_rank.p, n_p2 + 1);
-      LAUNCH(k_p2_lists, n_p2, ops.p, p2_ops.p, n_p2, merkle_rank.p, mlist.p, mpos.p, p2_run_start.p, bad.p);
-      P3R_HIP(hipMemsetAsync(p2_run_start.p + n_p2, 0, 4, s));
-      scan_u32(ctx, p2_run_start.p, p2_run_rank.p, n_p2 + 1);
-      uint32_t v2[2];
-      P3R_HIP(hipMemcpyAsync(&v2[0], p2_run_rank.p + n_p2, 4, hipMemcpyDeviceToHost, s));
-      P3R_HIP(copy_sync(s, &v2[1], merkle_rank.p + n_p2, 4, hipMemcpyDeviceToHost));
-      n_p2_runs = v2[0];
-      n_normal = n_p2 - v2[1];
-      LAUNCH(k_compact_marked, n_p2, p2_run_start.p, p2_run_rank.p, n_p2, p2_runs.p);
-      P3R_HIP(hipMemsetAsync(plevel.p, 0, n_p2 * 4, s));
-      P3R_HIP(hipMemsetAsync(phead.p, 0, (n_p2 + 1) * 4, s));
-    }
-    // rows of the width-32 table: predecessor links
-    DevBuf pw_sponge(n_pw + 2), pw_srank(n_pw + 2), pw_slist(std::max<size_t>(n_pw, 1)), pw_prev(std::max<size_t>(n_pw, 1)),
-        pw_level(std::max<size_t>(n_pw, 1)), pw_joined(std::max<size_t>(n_pw, 1));
-    size_t n_pw_sponge = 0;
-    if (n_pw) {
-      LAUNCH(k_pw_modes, n_pw, ops.p, pw_ops.p, n_pw, pw_sponge.p);
-      P3R_HIP(hipMemsetAsync(pw_sponge.p + n_pw, 0, 4, s));
-      scan_u32(ctx, pw_sponge.p, pw_srank.p, n_pw + 1);
-      uint32_t v = 0;
-      P3R_HIP(copy_sync(s, &v, pw_srank.p + n_pw, 4, hipMemcpyDeviceToHost));
-      n_pw_sponge = v;
-      LAUNCH(k_compact_marked, n_pw, pw_sponge.p, pw_srank.p, n_pw, pw_slist.p);
-      LAUNCH(k_pw_links, n_pw, ops.p, pw_ops.p, n_pw, pw_srank.p, pw_slist.p, pw_prev.p, bad.p);
-      P3R_HIP(hipMemsetAsync(pw_level.p, 0, n_pw * 4, s));
-      P3R_HIP(hipMemsetAsync(pw_joined.p, 0, n_pw * 4, s));
-    }
-    {
-      uint32_t b0 = 0;
-      P3R_HIP(copy_sync(s, &b0, bad.p, 4, hipMemcpyDeviceToHost));
-      if (b0) return false;
-    }
-    prof_stage(ctx, "prep_schedule_levels");
-    // levels
+    runs.alloc(at_least_one(n_members));
+    chead.alloc(at_least_one(n_members) + 1);
+    n_runs = prims::select_marked_count(s, run_start.p, n_members, run_rank.p, runs.p);
+    if (n_members) P3R_HIP(hipMemsetAsync(chead.p, 0, (n_members + 1) * 4, s));
+  }
+
+  // Poseidon2 rows by mode, and the runs of chained permutations
+  void p2_mode_lists() {
+    for (DevBuf* b : {&mlist, &mpos, &p2_runs, &plevel}) b->alloc(at_least_one(n_p2));
+    phead.alloc(n_p2 + 1);
+    if (!n_p2) return;
+    DevBuf is_merkle(n_p2), merkle_rank(n_p2 + 1), p2_run_start(n_p2), p2_run_rank(n_p2 + 1);
+    LAUNCH(k_p2_modes, n_p2, ops.p, p2_ops.p, n_p2, is_merkle.p);
+    prims::select_marked(s, is_merkle.p, n_p2, merkle_rank.p);
+    LAUNCH(k_p2_lists, n_p2, ops.p, p2_ops.p, n_p2, merkle_rank.p, mlist.p, mpos.p, p2_run_start.p, bad.p);
+    prims::select_marked(s, p2_run_start.p, n_p2, p2_run_rank.p, p2_runs.p);
+    uint32_t v2[2];
+    P3R_HIP(hipMemcpyAsync(&v2[0], p2_run_rank.p + n_p2, 4, hipMemcpyDeviceToHost, s));
+    P3R_HIP(copy_sync(s, &v2[1], merkle_rank.p + n_p2, 4, hipMemcpyDeviceToHost));
+    n_p2_runs = v2[0];
+    n_normal = n_p2 - v2[1];
+    P3R_HIP(hipMemsetAsync(plevel.p, 0, n_p2 * 4, s));
+    P3R_HIP(hipMemsetAsync(phead.p, 0, (n_p2 + 1) * 4, s));
+  }
+  // rows of the width-32 table: predecessor links
+  void w32_links() {
+    for (DevBuf* b : {&pw_sponge, &pw_slist, &pw_prev, &pw_level, &pw_joined}) b->alloc(at_least_one(n_pw));
+    pw_srank.alloc(n_pw + 1);
+    if (!n_pw) return;
+    LAUNCH(k_pw_modes, n_pw, ops.p, pw_ops.p, n_pw, pw_sponge.p);
+    n_pw_sponge = prims::select_marked_count(s, pw_sponge.p, n_pw, pw_srank.p, pw_slist.p);
+    LAUNCH(k_pw_links, n_pw, ops.p, pw_ops.p, n_pw, pw_srank.p, pw_slist.p, pw_prev.p, bad.p);
+    P3R_HIP(hipMemsetAsync(pw_level.p, 0, n_pw * 4, s));
+    P3R_HIP(hipMemsetAsync(pw_joined.p, 0, n_pw * 4, s));
+  }
+
+  // ---- prep_schedule_levels: level = 1 + max(level of what the op reads or compares against), to the fixed point
+  void schedule_levels() {
     for (int round = 0;; ++round) {
       P3R_HIP(hipMemsetAsync(changed.p, 0, 4, s));
       for (int k = 0; k < 4; ++k) {
@@ -1647,13 +1701,14 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
         LAUNCH(k_level_p2w, n_pw, ops.p, ext.p, pw_ops.p, n_pw, pw_prev.p, pw_sponge.p, stime.p, wlevel.p, pw_level.p, pw_joined.p,
                changed.p);
       }
-      uint32_t c = 0;
-      P3R_HIP(copy_sync(s, &c, changed.p, 4, hipMemcpyDeviceToHost));
-      if (!c) break;
+      if (!fetch_u32(ctx, changed.p)) break;
       if (round > (1 << 20)) fail(P3R_EINVAL, "circuit schedule did not converge");
     }
-    prof_stage(ctx, "prep_schedule_emit");
-    // ALU-dedup leftovers (runner.rs:199-216): duplicates take the value of their canonical witness after the last level
+  }
+
+  // ---- prep_schedule_emit: ALU-dedup leftovers (runner.rs:199-216): duplicates take the value of their canonical witness after
+  // the last level.  The one piece of host-side map work of the pass; then WitnessNotSetForIndex.
+  void witness_rewrites() {
     std::vector<uint32_t> rewrite_triples;
     if (d->n_rewrite) {
       std::unordered_map<uint32_t, uint32_t> canon_of;
@@ -1673,7 +1728,7 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
       }
       DevBuf d_need(need.size()), d_got(need.size());
       P3R_HIP(hipMemcpyAsync(d_need.p, need.data(), need.size() * 4, hipMemcpyHostToDevice, s));
-      LAUNCH(k_gather_u32, need.size(), stime.p, d_need.p, need.size(), d_got.p);
+      LAUNCH(prims::k_gather_u32, need.size(), stime.p, d_need.p, need.size(), d_got.p);
       std::vector<uint32_t> got = fetch<uint32_t>(ctx, d_got.p, need.size());
       std::unordered_map<uint32_t, bool> set;
       for (size_t k = 0; k < need.size(); ++k) set[need[k]] = got[k] != kUnset;
@@ -1692,17 +1747,17 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
       }
     }
     R.n_rewrite = rewrite_triples.size() / 3;
-    up(R.d_rewrite, rewrite_triples.data(), rewrite_triples.size());
+    up(ctx, R.d_rewrite, rewrite_triples.data(), rewrite_triples.size());
     LAUNCH(k_any_unset, nw, stime.p, nw, bad.p);  // WitnessNotSetForIndex
+  }
 
-    prof_stage(ctx, "prep_emit_light");
-    // ---- emission: level histograms and the level-sorted arrays
+  // ---- prep_emit_light: the deepest level, the histogram rows, the light ops sorted by level, the device ext array
+  bool emit_light() {
     DevBuf mxl(1);
     P3R_HIP(hipMemsetAsync(mxl.p, 0, 4, s));
     LAUNCH(k_max_u32, n_ops, olevel.p, n_ops, mxl.p);
     LAUNCH(k_max_u32, n_p2, plevel.p, n_p2, mxl.p);
     LAUNCH(k_max_u32, n_pw, pw_level.p, n_pw, mxl.p);
-    uint32_t max_level = 0;
     {
       uint32_t v2[2];
       P3R_HIP(hipMemcpyAsync(&v2[0], mxl.p, 4, hipMemcpyDeviceToHost, s));
@@ -1711,109 +1766,83 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
       max_level = v2[0];
     }
     S.levels = max_level;
-    const size_t nl1 = (size_t)max_level + 2;
-    const int lbits = bits_for(2 * max_level + 1);
-    // light ops: stable sort by level
-    DevBuf light_keys(std::max<size_t>(n_light, 1)), light_keys2(std::max<size_t>(n_light, 1)), light_sorted(std::max<size_t>(n_light, 1));
-    // first[key] per sorted array: light ops and segments by level, chains by level * 2 + (short ? 1 : 0)
-    DevBuf hist(4 * nl1);
+    nl1 = (size_t)max_level + 2;
+    lbits = bits_for(2 * max_level + 1);
+    hist.alloc(4 * nl1);
     P3R_HIP(hipMemsetAsync(hist.p, 0xFF, 4 * nl1 * 4, s));
-    uint32_t *f_light = hist.p, *f_seg = hist.p + nl1, *f_chain = hist.p + 2 * nl1;
-    LAUNCH(k_gather_u32, n_light, olevel.p, light_ops.p, n_light, light_keys.p);
-    sort_by_key(ctx, light_keys.p, light_keys2.p, light_ops.p, light_sorted.p, n_light, lbits);
-    LAUNCH(k_first_index, n_light, light_keys2.p, n_light, f_light);
-    R.d_light.alloc(std::max<size_t>(n_light * (sizeof(RunOp) / 4), 1));
-    LAUNCH(k_emit_light, n_light, ops.p, light_sorted.p, n_light, oflags.p, S_ap, S_re, s_rc.p, (uint32_t)n_rec_plain,
-           reinterpret_cast<RunOp*>(R.d_light.p));
-    R.d_ext.alloc(std::max<size_t>(n_dev_ext, 1));
-    LAUNCH(k_emit_ext<PP>, n_ops, ops.p, n_ops, ext.p, S_re, stime.p, D, R.d_ext.p);
-    prof_stage(ctx, "prep_emit_chains");
-    // Horner chains
-    size_t n_chains = 0;
-    R.d_chain_ops.alloc(std::max<size_t>(n_members * (sizeof(RunOp) / 4), 1));
+    // light ops: stable sort by level
+    DevBuf light_keys(at_least_one(n_light)), light_keys2(at_least_one(n_light)), light_sorted(at_least_one(n_light));
+    LAUNCH(prims::k_gather_u32, n_light, olevel.p, light_ops.p, n_light, light_keys.p);
+    prims::sort_pairs(s, light_keys.p, light_keys2.p, light_ops.p, light_sorted.p, n_light, lbits);
+    LAUNCH(prims::k_first_index, n_light, light_keys2.p, n_light, first_light());
+    R.d_light.alloc(at_least_one(n_light * (sizeof(RunOp) / 4)));
+    LAUNCH(k_emit_light, n_light, ops.p, light_sorted.p, n_light, oflags.p, S_ap(), S_re(), s_rc.p, (uint32_t)n_rec_plain, light());
+    R.d_ext.alloc(at_least_one(n_dev_ext));
+    LAUNCH(k_emit_ext<PP>, n_ops, ops.p, n_ops, ext.p, S_re(), stime.p, D, R.d_ext.p);
+    return true;
+  }
+
+  // ---- prep_emit_chains: Horner chains by (level, long first)
+  void emit_chains() {
+    R.d_chain_ops.alloc(at_least_one(n_members * (sizeof(RunOp) / 4)));
     R.d_chains.alloc(1);
-    if (n_members) {
-      LAUNCH(k_emit_chain_ops, n_members, ops.p, hmem.p, n_members, S_ap, S_re, reinterpret_cast<RunOp*>(R.d_chain_ops.p));
-      DevBuf ch_rank(n_members + 2), ch_heads(n_members);
-      scan_u32(ctx, chead.p, ch_rank.p, n_members + 1);
-      uint32_t v = 0;
-      P3R_HIP(copy_sync(s, &v, ch_rank.p + n_members, 4, hipMemcpyDeviceToHost));
-      n_chains = v;
-      LAUNCH(k_compact_marked, n_members, chead.p, ch_rank.p, n_members, ch_heads.p);
-      DevBuf segs(n_chains * 4), keys(n_chains), keys2(n_chains), lv(n_chains), iota(n_chains), order(n_chains);
-      LAUNCH(k_chain_records, n_chains, ops.p, hmem.p, ch_heads.p, n_chains, n_members, olevel.p,
-             reinterpret_cast<RunSchedule::ChainSeg*>(segs.p), keys.p, lv.p);
-      LAUNCH(k_iota, n_chains, iota.p, n_chains);
-      sort_by_key(ctx, keys.p, keys2.p, iota.p, order.p, n_chains, lbits);
-      LAUNCH(k_first_index, n_chains, keys2.p, n_chains, f_chain);
-      R.d_chains.alloc(n_chains * 4);
-      LAUNCH(k_permute_chains, n_chains, reinterpret_cast<RunSchedule::ChainSeg*>(segs.p), order.p, n_chains,
-             reinterpret_cast<RunSchedule::ChainSeg*>(R.d_chains.p));
-    }
-    prof_stage(ctx, "prep_emit_p2");
-    // Poseidon2 segments
-    size_t n_segs = 0;
-    R.d_p2.alloc(std::max<size_t>(n_p2 * ((D == 4 ? sizeof(RunP2) : sizeof(RunP2B)) / 4), 1));
+    if (!n_members) return;
+    LAUNCH(k_emit_chain_ops, n_members, ops.p, hmem.p, n_members, S_ap(), S_re(), chain_ops());
+    DevBuf ch_rank(n_members + 1), ch_heads(n_members);
+    n_chains = prims::select_marked_count(s, chead.p, n_members, ch_rank.p, ch_heads.p);
+    DevBuf segs(n_chains * 4), keys(n_chains), lv(n_chains), order(n_chains);
+    LAUNCH(k_chain_records, n_chains, ops.p, hmem.p, ch_heads.p, n_chains, n_members, olevel.p, as<RunSchedule::ChainSeg>(segs), keys.p, lv.p);
+    prims::order_by_level(s, keys.p, n_chains, lbits, first_chain(), order.p);
+    R.d_chains.alloc(n_chains * 4);
+    LAUNCH(k_permute_chains, n_chains, as<RunSchedule::ChainSeg>(segs), order.p, n_chains, chains());
+  }
+
+  // ---- prep_emit_p2: segments of the width-16 table by level
+  void emit_p2() {
+    R.d_p2.alloc(at_least_one(n_p2 * ((D == 4 ? sizeof(RunP2) : sizeof(RunP2B)) / 4)));
     R.d_p2segs.alloc(1);
-    if (n_p2) {
-      DevBuf head_by_row(n_p2 + 2), head_rank(n_p2 + 2), head_rows(n_p2);
-      LAUNCH(k_p2_head_by_row, n_p2, mlist.p, phead.p, n_p2, head_by_row.p);
-      P3R_HIP(hipMemsetAsync(head_by_row.p + n_p2, 0, 4, s));
-      scan_u32(ctx, head_by_row.p, head_rank.p, n_p2 + 1);
-      uint32_t v = 0;
-      P3R_HIP(copy_sync(s, &v, head_rank.p + n_p2, 4, hipMemcpyDeviceToHost));
-      n_segs = v;
-      LAUNCH(k_compact_marked, n_p2, head_by_row.p, head_rank.p, n_p2, head_rows.p);
-      DevBuf seg_pos(n_segs), seg_len(n_segs), seg_level(n_segs), keys2(n_segs), iota(n_segs), order(n_segs), len_sorted(n_segs + 1),
-          first(n_segs + 1);
-      LAUNCH(k_p2_seg_records, n_segs, head_rows.p, n_segs, mpos.p, phead.p, plevel.p, n_p2, n_normal, seg_pos.p, seg_len.p, seg_level.p);
-      LAUNCH(k_iota, n_segs, iota.p, n_segs);
-      sort_by_key(ctx, seg_level.p, keys2.p, iota.p, order.p, n_segs, lbits);
-      LAUNCH(k_first_index, n_segs, keys2.p, n_segs, f_seg);
-      LAUNCH(k_gather_u32, n_segs, seg_len.p, order.p, n_segs, len_sorted.p);
-      scan_u32(ctx, len_sorted.p, first.p, n_segs);
-      R.d_p2segs.alloc(n_segs * 2);
-      if (D == 4)
-        LAUNCH(k_emit_p2, n_segs, ops.p, ext.p, p2_ops.p, mlist.p, order.p, seg_pos.p, seg_len.p, first.p, n_segs, n_normal, stime.p,
-               reinterpret_cast<RunP2*>(R.d_p2.p), reinterpret_cast<RunSchedule::P2Seg*>(R.d_p2segs.p));
-      else
-        LAUNCH(k_emit_p2_base, n_segs, ops.p, ext.p, p2_ops.p, mlist.p, order.p, seg_pos.p, seg_len.p, first.p, n_segs, n_normal, stime.p,
-               reinterpret_cast<RunP2B*>(R.d_p2.p), reinterpret_cast<RunSchedule::P2Seg*>(R.d_p2segs.p));
-    }
-    // segments of the width-32 table: heads in row order (= the order the sequential walk opens them in), stable sort by level
-    size_t n_wsegs = 0;
-    DevBuf histw(nl1);
+    if (!n_p2) return;
+    DevBuf head_by_row(n_p2), head_rank(n_p2 + 1), head_rows(n_p2);
+    LAUNCH(k_p2_head_by_row, n_p2, mlist.p, phead.p, n_p2, head_by_row.p);
+    n_segs = prims::select_marked_count(s, head_by_row.p, n_p2, head_rank.p, head_rows.p);
+    DevBuf seg_pos(n_segs), seg_len(n_segs), seg_level(n_segs), order(n_segs), seg_first(n_segs);
+    LAUNCH(k_p2_seg_records, n_segs, head_rows.p, n_segs, mpos.p, phead.p, plevel.p, n_p2, n_normal, seg_pos.p, seg_len.p, seg_level.p);
+    prims::order_by_level(s, seg_level.p, n_segs, lbits, first_seg(), order.p, seg_len.p, seg_first.p);
+    R.d_p2segs.alloc(n_segs * 2);
+    if (D == 4)
+      LAUNCH(k_emit_p2, n_segs, ops.p, ext.p, p2_ops.p, mlist.p, order.p, seg_pos.p, seg_len.p, seg_first.p, n_segs, n_normal, stime.p,
+             as<RunP2>(R.d_p2), p2segs());
+    else
+      LAUNCH(k_emit_p2_base, n_segs, ops.p, ext.p, p2_ops.p, mlist.p, order.p, seg_pos.p, seg_len.p, seg_first.p, n_segs, n_normal, stime.p,
+             as<RunP2B>(R.d_p2), p2segs());
+  }
+  // segments of the width-32 table: heads in row order (= the order the sequential walk opens them in), by level
+  void emit_p2w() {
+    histw.alloc(nl1);
     P3R_HIP(hipMemsetAsync(histw.p, 0xFF, nl1 * 4, s));
-    if (n_pw) {
-      DevBuf is_head(n_pw + 2), head_rank(n_pw + 2), head_rows(n_pw);
-      LAUNCH(k_pw_heads, n_pw, pw_joined.p, n_pw, is_head.p);
-      P3R_HIP(hipMemsetAsync(is_head.p + n_pw, 0, 4, s));
-      scan_u32(ctx, is_head.p, head_rank.p, n_pw + 1);
-      uint32_t v = 0;
-      P3R_HIP(copy_sync(s, &v, head_rank.p + n_pw, 4, hipMemcpyDeviceToHost));
-      n_wsegs = v;
-      LAUNCH(k_compact_marked, n_pw, is_head.p, head_rank.p, n_pw, head_rows.p);
-      DevBuf seg_len(n_wsegs), seg_level(n_wsegs), keys2(n_wsegs), iota(n_wsegs), order(n_wsegs), len_sorted(n_wsegs + 1), first(n_wsegs + 1);
-      LAUNCH(k_pw_seg_records, n_wsegs, head_rows.p, n_wsegs, n_pw, pw_prev.p, pw_joined.p, pw_sponge.p, pw_srank.p, pw_slist.p, n_pw_sponge,
-             pw_level.p, seg_len.p, seg_level.p);
-      LAUNCH(k_iota, n_wsegs, iota.p, n_wsegs);
-      sort_by_key(ctx, seg_level.p, keys2.p, iota.p, order.p, n_wsegs, lbits);
-      LAUNCH(k_first_index, n_wsegs, keys2.p, n_wsegs, histw.p);
-      LAUNCH(k_gather_u32, n_wsegs, seg_len.p, order.p, n_wsegs, len_sorted.p);
-      scan_u32(ctx, len_sorted.p, first.p, n_wsegs);
-      R.d_p2w.alloc(n_pw * (sizeof(RunP2W) / 4));
-      R.d_p2wsegs.alloc(n_wsegs * 2);
-      LAUNCH(k_emit_p2w, n_wsegs, ops.p, ext.p, pw_ops.p, n_pw, pw_prev.p, pw_joined.p, pw_sponge.p, pw_srank.p, pw_slist.p, n_pw_sponge,
-             order.p, head_rows.p, seg_len.p, first.p, n_wsegs, stime.p, reinterpret_cast<RunP2W*>(R.d_p2w.p),
-             reinterpret_cast<RunSchedule::P2Seg*>(R.d_p2wsegs.p));
-    }
-    prof_stage(ctx, "prep_emit_rest");
-    // static Const trace, Public gather list
-    R.d_const_values.alloc(std::max<size_t>(n_const * D, 1));
+    if (!n_pw) return;
+    DevBuf is_head(n_pw), head_rank(n_pw + 1), head_rows(n_pw);
+    LAUNCH(k_pw_heads, n_pw, pw_joined.p, n_pw, is_head.p);
+    n_wsegs = prims::select_marked_count(s, is_head.p, n_pw, head_rank.p, head_rows.p);
+    DevBuf seg_len(n_wsegs), seg_level(n_wsegs), order(n_wsegs), seg_first(n_wsegs);
+    LAUNCH(k_pw_seg_records, n_wsegs, head_rows.p, n_wsegs, n_pw, pw_prev.p, pw_joined.p, pw_sponge.p, pw_srank.p, pw_slist.p, n_pw_sponge,
+           pw_level.p, seg_len.p, seg_level.p);
+    prims::order_by_level(s, seg_level.p, n_wsegs, lbits, histw.p, order.p, seg_len.p, seg_first.p);
+    R.d_p2w.alloc(n_pw * (sizeof(RunP2W) / 4));
+    R.d_p2wsegs.alloc(n_wsegs * 2);
+    LAUNCH(k_emit_p2w, n_wsegs, ops.p, ext.p, pw_ops.p, n_pw, pw_prev.p, pw_joined.p, pw_sponge.p, pw_srank.p, pw_slist.p, n_pw_sponge,
+           order.p, head_rows.p, seg_len.p, seg_first.p, n_wsegs, stime.p, as<RunP2W>(R.d_p2w), p2wsegs());
+  }
+
+  // ---- prep_emit_rest: static Const trace, Public gather list
+  void emit_rest() {
+    R.d_const_values.alloc(at_least_one(n_const * D));
     LAUNCH(k_const_values<PP>, n_const * D, ops.p, ext.p, const_ops.p, n_const, D, R.d_const_values.p);
-    R.d_public_out.alloc(std::max<size_t>(n_public, 1));
+    R.d_public_out.alloc(at_least_one(n_public));
     LAUNCH(k_outs_of, n_public, ops.p, public_ops.p, n_public, R.d_public_out.p);
-    // per-level offsets on the host, launch plan
+  }
+  // per-level offsets on the host, launch plan
+  void level_offsets() {
     std::vector<uint32_t> hh = fetch<uint32_t>(ctx, hist.p, 4 * nl1);
     // offsets[k] = first position with key >= k: a key that does not occur starts where the next one does
     auto offsets = [&](const uint32_t* first, size_t n_keys, size_t n_items) {
@@ -1838,15 +1867,48 @@ bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
       S.p2wseg_off = offsets(hw.data(), nl1 - 1, n_wsegs);
       if (S.p2wseg_off.back() != n_wsegs)
         fail(P3R_EINVAL, "circuit schedule: level histogram does not add up (%u/%zu width-32 segments)", S.p2wseg_off.back(), n_wsegs);
-      up(R.d_p2wseg_off, S.p2wseg_off.data(), S.p2wseg_off.size());
+      up(ctx, R.d_p2wseg_off, S.p2wseg_off.data(), S.p2wseg_off.size());
     }
     finish_segments(S);
-    up(R.d_light_off, S.light_off.data(), S.light_off.size());
-    up(R.d_p2seg_off, S.p2seg_off.data(), S.p2seg_off.size());
-    up(R.d_chunk_bounds, S.chunk_bounds.data(), S.chunk_bounds.size());
+    up(ctx, R.d_light_off, S.light_off.data(), S.light_off.size());
+    up(ctx, R.d_p2seg_off, S.p2seg_off.data(), S.p2seg_off.size());
+    up(ctx, R.d_chunk_bounds, S.chunk_bounds.data(), S.chunk_bounds.size());
   }
+};
+
+template <class PP>
+bool devprep_impl(p3r_ctx* ctx, const p3r_circuit_desc* d, DevPrep& R) {
+  if (d->witness_count >= (1u << 31) || d->n_ops >= (size_t(1) << 28) || d->n_ops == 0 || d->witness_count == 0)
+    return false;  // host path: limits, degenerate circuits
+  const uint32_t D = ctx->cfg.ext_degree;
+  if (D != 1 && D != 4 && D != 5) return false;   // (the runner computes in these degrees)
+  PrepWork<PP> w(ctx, d, R);
+  prof_stage(ctx, "prep_upload");
+  if (!w.upload_and_validate()) return false;
+  prof_stage(ctx, "prep_bus_roles");
+  w.table_ranks_and_lists();
+  w.first_touches();
+  w.bus_roles();
+  prof_stage(ctx, "prep_traces");
+  w.traces();
+  prof_stage(ctx, "prep_schedule_static");
+  if (!w.schedule_static()) return false;
+  prof_stage(ctx, "prep_schedule_levels");
+  w.schedule_levels();
+  prof_stage(ctx, "prep_schedule_emit");
+  w.witness_rewrites();
+  prof_stage(ctx, "prep_emit_light");
+  if (!w.emit_light()) return false;
+  prof_stage(ctx, "prep_emit_chains");
+  w.emit_chains();
+  prof_stage(ctx, "prep_emit_p2");
+  w.emit_p2();
+  w.emit_p2w();
+  prof_stage(ctx, "prep_emit_rest");
+  w.emit_rest();
+  w.level_offsets();
   P3R_HIP(hipGetLastError());
-  P3R_HIP(hipStreamSynchronize(s));
+  P3R_HIP(hipStreamSynchronize(ctx->stream));
   return true;
 }
 
