@@ -76,6 +76,8 @@ struct TreeImpl : TreeBase {
 template <class FP>
 void do_permute(const uint32_t* rc, const uint32_t* in, uint32_t* out, size_t n) {
   Poseidon2<FP> p2(rc);
+  // the states are independent (tests/mmcs_ref.py permutes a whole tree layer per call)
+#pragma omp parallel for schedule(static) if (n >= 1024)
   for (size_t i = 0; i < n; ++i) {
     std::array<Fe<FP>, WIDTH> s;
     for (int k = 0; k < WIDTH; ++k) s[k] = Fe<FP>(in[i * WIDTH + k]);
@@ -245,6 +247,7 @@ int orc_p2w_permute(int field, const uint32_t* rc, const uint32_t* diag, const u
     auto run = [&](auto tag) {
       using FP = decltype(tag);
       Poseidon2W32<FP> p2(rc, diag);
+#pragma omp parallel for schedule(static) if (n >= 1024)
       for (size_t i = 0; i < n; ++i) {
         std::array<Fe<FP>, WIDTH32> s;
         for (int k = 0; k < WIDTH32; ++k) s[k] = Fe<FP>(in[i * WIDTH32 + k]);
