@@ -588,7 +588,8 @@ int p3r_fri_log_arity(const p3r_ctx* ctx, size_t phase, int log_cur, int log_fin
 enum {
   P3R_AIR_CHALLENGE = 8, P3R_AIR_LOCAL = 9, P3R_AIR_NEXT = 10, P3R_AIR_LOCAL_EXT = 11, P3R_AIR_NEXT_EXT = 12,
   P3R_AIR_IS_FIRST_ROW = 13, P3R_AIR_IS_LAST_ROW = 14, P3R_AIR_IS_TRANSITION = 15,
-  P3R_AIR_ADD = 16, P3R_AIR_SUB = 17, P3R_AIR_MUL = 18, P3R_AIR_NEG = 19, P3R_AIR_ASSERT_ZERO = 20
+  P3R_AIR_ADD = 16, P3R_AIR_SUB = 17, P3R_AIR_MUL = 18, P3R_AIR_NEG = 19, P3R_AIR_ASSERT_ZERO = 20,
+  P3R_AIR_LOOKUP = 21, P3R_AIR_LOOKUP_END = 22   /* lookup programs only (below); unknown ops to the two entries above */
 };
 #define P3R_AIR_MAX_LIVE 48
 typedef struct p3r_air_insn {
@@ -607,6 +608,75 @@ int p3r_quotient_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_i
                               const uint32_t* public_values, size_t n_public,
                               const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
                               const uint32_t* alpha /* DC */, p3r_dmat** outs /* 2^log_quotient_degree */);
+
+/* ---- the caller's lookups: lookup programs build the permutation (LogUp) trace of resident traces ----
+ *
+ * Functions are only added: P3R_ABI_VERSION stays as it is.
+ *
+ * The step of a prover between the trace commitment and the quotient for an AIR on a bus: p3_lookup's LogUp gadget
+ * (LogUpGadget: one auxiliary column per packed group of interactions, the fractions sum_k m_k / d_k, and the running sum
+ * over the rows) for interactions the CALLER brings.  The auxiliary trace it returns is the matrix P3R_AIR_LOCAL_EXT /
+ * P3R_AIR_NEXT_EXT read: it goes to p3r_coset_lde_dmat, p3r_mmcs_commit_dmat and p3r_quotient_program_dmat as it is.
+ *
+ * A lookup program is a p3r_air_insn array in the SSA form above, with other sinks:
+ *
+ *   P3R_AIR_LOOKUP             a = multiplicity value id,                 none (it may not be referenced): adds the term
+ *                              b = denominator value id                   m / d to the open auxiliary column, and opens
+ *                                                                         one if none is open
+ *   P3R_AIR_LOOKUP_END         none                                       none: closes the open column
+ *
+ * Multiplicity and denominator are base or extension values; a base value is lifted.  The denominator is program data:
+ * the seam fixes no bus convention.  The reference's form, bus_prefix + sum_j beta^j * field_j with the challenges laid out
+ * [bus_prefix, beta] per lookup (recursion/src/verifier/batch_stark.rs:1086-1110), is a few CHALLENGE / MUL / ADD
+ * instructions.  Nor does it fix a packing: the caller groups terms into columns with LOOKUP_END, as pack_same_bus does
+ * under its degree budget.  ASSERT_ZERO and the three selectors are refused in a lookup program (upstream's trace-domain
+ * values of the selectors are un-vendored and not guessed); LOOKUP and LOOKUP_END stay unknown ops to
+ * p3r_air_program_info and p3r_quotient_program_dmat.
+ *
+ * Semantics.  All input matrices are TRACES on the trace domain: h rows (a power of two), natural order, not LDEs.  Row
+ * r is the current row, (r + 1) mod h the next (h = 1: the row itself).  With G closed columns:
+ *   f_g[r] = sum over the terms k of column g of m_k(r) / d_k(r);
+ *   s[0] = 0,  s[r + 1] = s[r] + sum_g f_g[r]  - the exclusive prefix, as the prover's own auxiliary trace has it in column 0;
+ *   T = s[h - 1] + sum_g f_g[h - 1], the table's sum.
+ * *out is one fresh h x DC * (1 + G) matrix the caller frees: columns [0, DC) hold the coefficients of s, columns
+ * [DC * (1 + g), DC * (2 + g)) those of f_g.  T goes to sum_out (HOST, DC canonical words): the caller's challenger
+ * observes it, so p3r_logup_program_dmat WAITS for the stream, unlike p3r_quotient_program_dmat.
+ *
+ * The constraints the caller then writes in its constraint program ("LogUp per-row constraints"), with
+ * f_g = LOCAL_EXT(aux, DC * (1 + g)), s = LOCAL_EXT(aux, 0), s' = NEXT_EXT(aux, 0) and T a challenge:
+ *   f_g * prod_k d_k - sum_k m_k * prod_{l != k} d_l    for each column g
+ *   is_first_row * s
+ *   is_transition * (s' - s - sum_g f_g)
+ *   is_last_row * (s + sum_g f_g - T)
+ * The first has the degree max(1 + sum_k deg d_k, max_k(deg m_k + sum_{l != k} deg d_l)) under the degree rule above;
+ * p3r_lookup_program_info reports the largest over the columns, which the quotient's log_quotient_degree must admit.
+ *
+ * A zero denominator: upstream divides by zero there.  Here no wrong trace is returned: the call frees the output and
+ * returns P3R_EINVAL with "zero denominator in row R", R the smallest row in which the denominator product of a column
+ * vanishes.  The context stays usable.
+ *
+ * p3r_lookup_program_info (host only, no context, as p3r_air_program_info) validates a program against the matrix widths
+ * and reports n_terms, n_columns, max_terms_per_column, max_constraint_degree and peak_live.  P3R_OK, or the refusal
+ * p3r_logup_program_dmat would give for the program (message: p3r_last_error(NULL)).
+ *
+ * Refusals of p3r_logup_program_dmat, with a message, before anything is allocated or launched.  P3R_EINVAL: what
+ * p3r_quotient_program_dmat refuses about operands, ops, matrices, columns, indices and non-canonical words; an ASSERT_ZERO
+ * or a selector; a LOOKUP operand that is not an earlier value or is a LOOKUP / LOOKUP_END; a LOOKUP_END with no open
+ * column; a program that ends with a column open; no LOOKUP; n_mats == 0; matrices of different heights; a height that
+ * is not a power of two or is above 2^TWO_ADICITY; a NULL out or sum_out.  P3R_EUNSUPPORTED: more live values than
+ * P3R_AIR_MAX_LIVE (the interpreter keeps them in LDS exactly as above; LOOKUP and LOOKUP_END take no slot); zk contexts. */
+typedef struct p3r_lookup_info {
+  uint32_t n_terms, n_columns;
+  uint32_t max_terms_per_column;
+  uint32_t max_constraint_degree;   /* largest column-constraint degree: what the caller's quotient budget must admit */
+  uint32_t peak_live;
+} p3r_lookup_info;
+int p3r_lookup_program_info(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
+                            p3r_lookup_info* out);
+int p3r_logup_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,
+                           const uint32_t* public_values, size_t n_public,
+                           const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
+                           p3r_dmat** out, uint32_t* sum_out /* DC, HOST */);
 
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *

@@ -10,6 +10,7 @@
 //   NonPrimitiveTableEntry       :272-290        BatchStarkProof  :610-636 (+ validate :666-681)
 //   BatchStarkProver::{prove_all_tables, verify_all_tables}   :1203-1268
 //   AirProgram, quotient_values  p3_uni_stark::{SymbolicAirBuilder, prove's quotient_values + split_evals}
+//   AirProgram::lookup, logup_trace  p3_lookup's LogUp gadget: the permutation trace and the table's sum
 //   DuplexChallenger, TwoAdicFriFolding, prove_fri   p3_challenger::DuplexChallenger, p3_fri::{TwoAdicFriFolding, prover::prove_fri}
 //   Circuit<EF> / CircuitRunner  circuit/src/circuit.rs:152-181, circuit/src/tables/runner.rs:22-253
 //   FriRecursionBackend          recursion/src/backend/fri.rs:113-128
@@ -272,6 +273,10 @@ class AirProgram {
   Value is_last_row() { return emit(P3R_AIR_IS_LAST_ROW); }
   Value is_transition() { return emit(P3R_AIR_IS_TRANSITION); }
   void assert_zero(Value v) { emit(P3R_AIR_ASSERT_ZERO, v.id); }
+  // the sinks of a lookup program (logup_trace): the term multiplicity / denominator joins the open auxiliary column
+  // (one is opened if none is open); end_lookup_column closes it
+  void lookup(Value multiplicity, Value denominator) { emit(P3R_AIR_LOOKUP, multiplicity.id, denominator.id); }
+  void end_lookup_column() { emit(P3R_AIR_LOOKUP_END); }
   Value emit(uint32_t op, uint32_t a = 0, uint32_t b = 0) {
     insns_.push_back(p3r_air_insn{op, a, b});
     return Value{this, (uint32_t)insns_.size() - 1};
@@ -281,6 +286,13 @@ class AirProgram {
   p3r_air_info info(const Context& ctx, const std::vector<size_t>& widths) const {
     p3r_air_info out{};
     const int rc = p3r_air_program_info(&ctx.config(), insns_.data(), insns_.size(), widths.data(), widths.size(), &out);
+    if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
+    return out;
+  }
+  // of a lookup program: n_terms, n_columns, max_terms_per_column, max_constraint_degree, peak_live - or the refusal
+  p3r_lookup_info lookup_info(const Context& ctx, const std::vector<size_t>& widths) const {
+    p3r_lookup_info out{};
+    const int rc = p3r_lookup_program_info(&ctx.config(), insns_.data(), insns_.size(), widths.data(), widths.size(), &out);
     if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
     return out;
   }
@@ -311,6 +323,26 @@ inline std::vector<p3r_dmat*> quotient_values(const Context& ctx, const AirProgr
                                       shift, log_quotient_degree, public_values.data(), public_values.size(), challenges.data(),
                                       challenges.size() / dc, alpha.data(), outs.data()));
   return outs;
+}
+
+// p3_lookup's LogUp gadget over device matrices (p3r.h: p3r_logup_program_dmat): `mats` are the TRACES of one table (one
+// height h, natural order, not LDEs), `program` a lookup program (AirProgram::lookup / end_lookup_column as its sinks).
+// `trace` is the h x DC * (1 + G) auxiliary trace - the running sum in its first DC columns, then the fractions of each
+// closed column, the flattening local_ext reads - which the caller frees; `sum` the DC canonical words of the table's
+// sum.  Waits for the device; a zero denominator is an Error (P3R_EINVAL) naming the row.
+struct LogupTrace {
+  p3r_dmat* trace;
+  std::vector<uint32_t> sum;
+};
+inline LogupTrace logup_trace(const Context& ctx, const AirProgram& program, const std::vector<const p3r_dmat*>& mats,
+                              const std::vector<uint32_t>& public_values = {}, const std::vector<uint32_t>& challenges = {}) {
+  const size_t dc = ctx.config().challenge_degree ? ctx.config().challenge_degree : 4;
+  if (challenges.size() % dc) throw Error(P3R_EINVAL, "challenges are DC words each");
+  LogupTrace out{nullptr, std::vector<uint32_t>(dc, 0)};
+  ctx.check(p3r_logup_program_dmat(ctx.raw(), program.insns().data(), program.insns().size(), mats.data(), mats.size(),
+                                   public_values.data(), public_values.size(), challenges.data(), challenges.size() / dc, &out.trace,
+                                   out.sum.data()));
+  return out;
 }
 
 // DuplexChallenger<F, Perm16, 16, 8> of circuit-prover/src/config.rs over the context's Poseidon2 constants (p3r.h:

@@ -20,6 +20,8 @@ P3R_EXT_ZK_DETERMINISTIC = 4        # ZK key taken as it is, p3r_zk_set_nonce al
 (P3R_AIR_CONST, P3R_AIR_PUBLIC, P3R_AIR_CHALLENGE, P3R_AIR_LOCAL, P3R_AIR_NEXT, P3R_AIR_LOCAL_EXT, P3R_AIR_NEXT_EXT,
  P3R_AIR_IS_FIRST_ROW, P3R_AIR_IS_LAST_ROW, P3R_AIR_IS_TRANSITION, P3R_AIR_ADD, P3R_AIR_SUB, P3R_AIR_MUL, P3R_AIR_NEG,
  P3R_AIR_ASSERT_ZERO) = (0, 1) + tuple(range(8, 21))
+# the sinks of a lookup program (p3r_logup_program_dmat); unknown ops to the constraint-program entries
+P3R_AIR_LOOKUP, P3R_AIR_LOOKUP_END = 21, 22
 P3R_AIR_MAX_LIVE = 48
 FIELD_KOALA_BEAR = 0
 FIELD_BABY_BEAR = 1
@@ -89,6 +91,11 @@ class P3rAirInsn(C.Structure):
 class P3rAirInfo(C.Structure):
     _fields_ = [("n_constraints", C.c_uint32), ("max_degree", C.c_uint32), ("log_quotient_degree", C.c_uint32),
                 ("peak_live", C.c_uint32)]
+
+
+class P3rLookupInfo(C.Structure):
+    _fields_ = [("n_terms", C.c_uint32), ("n_columns", C.c_uint32), ("max_terms_per_column", C.c_uint32),
+                ("max_constraint_degree", C.c_uint32), ("peak_live", C.c_uint32)]
 
 
 class P3rAirDesc(C.Structure):
@@ -239,6 +246,11 @@ SIGNATURES = {
                                        C.POINTER(P3rAirInfo)]),
     "p3r_quotient_program_dmat": (C.c_int, [vp, C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(vp), C.c_size_t, C.c_uint32, C.c_uint32,
                                             C.c_uint32, u32p, C.c_size_t, u32p, C.c_size_t, u32p, C.POINTER(vp)]),
+    # the caller's lookups as a lookup program (the LogUp auxiliary trace of resident traces)
+    "p3r_lookup_program_info": (C.c_int, [C.POINTER(P3rConfig), C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
+                                          C.POINTER(P3rLookupInfo)]),
+    "p3r_logup_program_dmat": (C.c_int, [vp, C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(vp), C.c_size_t, u32p, C.c_size_t, u32p,
+                                         C.c_size_t, C.POINTER(vp), u32p]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

@@ -1,8 +1,11 @@
-// The host half of the constraint-program seam (p3r_air_program_info, p3r_quotient_program_dmat; include/p3r.h): what is
-// decided about a caller's p3r_air_insn program before anything touches the device.  Host only, no HIP and no context:
-// tu_air.hip turns a plan into a launch, tests/air_program_host_main.cpp walks it with g++ alone.
+// The host half of the constraint-program seam (p3r_air_program_info, p3r_quotient_program_dmat; include/p3r.h) and of
+// the lookup-program seam (p3r_lookup_program_info, p3r_logup_program_dmat): what is decided about a caller's p3r_air_insn
+// program before anything touches the device.  Host only, no HIP and no context: tu_air.hip turns a plan into a launch,
+// tests/air_program_host_main.cpp and tests/lookup_program_host_main.cpp walk it with g++ alone.
 //
-//   air_plan      validation, typing (base / extension), the degree walk, liveness and the assignment of values to slots
+//   air_plan      validation, typing (base / extension), the degree walk, liveness and the assignment of values to slots;
+//                 in AIR_MODE_LOOKUP the sinks are P3R_AIR_LOOKUP / P3R_AIR_LOOKUP_END instead of ASSERT_ZERO, and the
+//                 degree reported is that of each auxiliary column's constraint
 //   air_compile   the instruction stream the interpreter reads: operands as LDS word offsets, ops specialised by the
 //                 operand types, constants and public values in Montgomery form, challenges in a side table
 //   air_domain    the per-chunk constants of the quotient domain: x^h - 1 and its inverse on each of the 2^q cosets
@@ -34,19 +37,27 @@ constexpr size_t kAirMaxLdsBytes = (size_t)P3R_AIR_MAX_LIVE * (kMaxAirDC + 1) * 
 constexpr uint32_t kAirNoSlot = 0xffffffffu;
 constexpr size_t kAirUnknownCount = ~size_t(0);   // n_public / n_challenges of p3r_air_program_info: not checked
 
+// What a program's sinks are: the constraints of the quotient seam, or the terms and columns of the lookup seam.
+enum AirMode { AIR_MODE_CONSTRAINTS, AIR_MODE_LOOKUP };
+
 inline bool air_op_is_binary(uint32_t op) { return op == P3R_AIR_ADD || op == P3R_AIR_SUB || op == P3R_AIR_MUL; }
-inline bool air_op_known(uint32_t op) {
-  return op == P3R_AIR_CONST || op == P3R_AIR_PUBLIC || (op >= P3R_AIR_CHALLENGE && op <= P3R_AIR_ASSERT_ZERO);
+inline bool air_op_known(uint32_t op, AirMode mode = AIR_MODE_CONSTRAINTS) {
+  return op == P3R_AIR_CONST || op == P3R_AIR_PUBLIC || (op >= P3R_AIR_CHALLENGE && op <= P3R_AIR_ASSERT_ZERO) ||
+         (mode == AIR_MODE_LOOKUP && (op == P3R_AIR_LOOKUP || op == P3R_AIR_LOOKUP_END));
 }
+// an instruction that defines no value
+inline bool air_op_is_sink(uint32_t op) { return op == P3R_AIR_ASSERT_ZERO || op == P3R_AIR_LOOKUP || op == P3R_AIR_LOOKUP_END; }
 // number of value operands
 inline int air_op_operands(uint32_t op) {
-  return air_op_is_binary(op) ? 2 : (op == P3R_AIR_NEG || op == P3R_AIR_ASSERT_ZERO) ? 1 : 0;
+  return air_op_is_binary(op) || op == P3R_AIR_LOOKUP ? 2 : (op == P3R_AIR_NEG || op == P3R_AIR_ASSERT_ZERO) ? 1 : 0;
 }
 
 struct AirPlan {
   p3r_air_info info{};
+  p3r_lookup_info lookup{};         // AIR_MODE_LOOKUP
+  std::vector<uint32_t> column_degree;   // AIR_MODE_LOOKUP: the degree of each closed column's constraint
   std::vector<uint8_t> is_ext;      // per value
-  std::vector<uint32_t> slot;       // per value: its slot in the region of its kind; kAirNoSlot for an ASSERT_ZERO
+  std::vector<uint32_t> slot;       // per value: its slot in the region of its kind; kAirNoSlot for a sink
   std::vector<uint32_t> last_use;   // per value: the last instruction that reads it (its own index: never read)
   uint32_t n_base_slots = 0, n_ext_slots = 0;
   bool uses_x = false;              // a selector: the lane needs its point x
@@ -64,11 +75,27 @@ inline uint32_t air_log_quotient_degree(uint64_t max_degree) {
   return l;
 }
 
+// What the lookup seam refuses about the height of its traces: here, so that it is checked without a device.
+inline int air_trace_log_height(size_t h, int two_adicity) {
+  if (h == 0 || (h & (h - 1))) fail(P3R_EINVAL, "matrix height (%zu) must be a power of two: the traces of a table live on a two-adic domain", h);
+  int l = 0;
+  while ((size_t(1) << l) < h) ++l;
+  if (l > two_adicity) fail(P3R_EINVAL, "2^%d rows exceed the field's two-adicity (%d)", l, two_adicity);
+  return l;
+}
+
 // Everything that can be refused about a program on its own.  p: the field's modulus; dc: the challenge degree;
 // n_public / n_challenges: kAirUnknownCount leaves the indices unchecked; max_live: P3R_AIR_MAX_LIVE.
+//
+// AIR_MODE_LOOKUP: a LOOKUP (a = multiplicity, b = denominator) adds the term m / d to the open auxiliary column and
+// opens one if none is open; LOOKUP_END closes it.  The constraint of a column, f * prod_k d_k - sum_k m_k prod_{l != k} d_l,
+// has the degree max(1 + sum_k deg d_k, max_k(deg m_k + sum_{l != k} deg d_l)): kept per open column as the two running
+// figures den_deg = sum_k deg d_k and num_deg = max_k(deg m_k + sum_{l != k} deg d_l) over the terms met so far.  A lookup
+// program has no constraints of its own and no selectors.
 inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths, size_t n_mats, int dc, uint32_t p,
-                        size_t n_public, size_t n_challenges, uint32_t max_live) {
-  if (n == 0 || !prog) fail(P3R_EINVAL, "the program has no ASSERT_ZERO (it is empty)");
+                        size_t n_public, size_t n_challenges, uint32_t max_live, AirMode mode = AIR_MODE_CONSTRAINTS) {
+  const bool lookup = mode == AIR_MODE_LOOKUP;
+  if (n == 0 || !prog) fail(P3R_EINVAL, lookup ? "the program has no LOOKUP (it is empty)" : "the program has no ASSERT_ZERO (it is empty)");
   if (n > 0x7fffffffu) fail(P3R_EINVAL, "the program is too long");
   if (n_mats && !widths) fail(P3R_EINVAL, "widths is NULL");
   constexpr uint64_t kDegCap = uint64_t(1) << 40;   // saturates: a chain of squarings must not wrap
@@ -77,17 +104,24 @@ inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths
   pl.slot.assign(n, kAirNoSlot);
   pl.last_use.resize(n);
   std::vector<uint64_t> deg(n, 0);
-  std::vector<uint8_t> is_assert(n, 0);
+  std::vector<uint8_t> is_assert(n, 0);   // a sink: it has no value
   uint64_t max_deg = 0;
+  bool column_open = false;
+  uint64_t den_deg = 0, num_deg = 0;      // of the open column
+  uint32_t column_terms = 0;
   for (size_t i = 0; i < n; ++i) {
     const p3r_air_insn& in = prog[i];
     pl.last_use[i] = (uint32_t)i;
-    if (!air_op_known(in.op)) fail(P3R_EINVAL, "instruction %zu: unknown op %u", i, in.op);
+    if (!air_op_known(in.op, mode)) fail(P3R_EINVAL, "instruction %zu: unknown op %u", i, in.op);
+    if (lookup && in.op == P3R_AIR_ASSERT_ZERO) fail(P3R_EINVAL, "instruction %zu: ASSERT_ZERO in a lookup program, which has no constraints", i);
+    if (lookup && (in.op == P3R_AIR_IS_FIRST_ROW || in.op == P3R_AIR_IS_LAST_ROW || in.op == P3R_AIR_IS_TRANSITION))
+      fail(P3R_EINVAL, "instruction %zu: a selector (op %u) in a lookup program: selectors have no value on the trace domain here", i, in.op);
     const int n_ops = air_op_operands(in.op);
     const uint32_t ops[2] = {in.a, in.b};
     for (int k = 0; k < n_ops; ++k) {
       if (ops[k] >= i) fail(P3R_EINVAL, "instruction %zu: operand %u is not an earlier value", i, ops[k]);
-      if (is_assert[ops[k]]) fail(P3R_EINVAL, "instruction %zu: operand %u is an ASSERT_ZERO, which has no value", i, ops[k]);
+      if (is_assert[ops[k]])
+        fail(P3R_EINVAL, "instruction %zu: operand %u is %s, which has no value", i, ops[k], lookup ? "a LOOKUP or LOOKUP_END" : "an ASSERT_ZERO");
       pl.last_use[ops[k]] = (uint32_t)i;
     }
     switch (in.op) {
@@ -134,11 +168,41 @@ inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths
         ++pl.info.n_constraints;
         max_deg = std::max(max_deg, deg[in.a]);
         break;
+      case P3R_AIR_LOOKUP:   // a = m, b = d: every earlier numerator gains d, the new one is m * (the denominators so far)
+        is_assert[i] = 1;
+        if (!column_open) {   // the first term of a column: the numerator is m alone, the denominator product d
+          column_open = true;
+          num_deg = deg[in.a];
+          den_deg = deg[in.b];
+          column_terms = 0;
+        } else {
+          num_deg = std::min(std::max(num_deg + deg[in.b], deg[in.a] + den_deg), kDegCap);
+          den_deg = std::min(den_deg + deg[in.b], kDegCap);
+        }
+        ++pl.lookup.n_terms;
+        pl.lookup.max_terms_per_column = std::max(pl.lookup.max_terms_per_column, ++column_terms);
+        break;
+      case P3R_AIR_LOOKUP_END: {
+        is_assert[i] = 1;
+        if (!column_open) fail(P3R_EINVAL, "instruction %zu: LOOKUP_END with no open column", i);
+        column_open = false;
+        const uint64_t d = std::max(1 + den_deg, num_deg);
+        pl.column_degree.push_back((uint32_t)std::min<uint64_t>(d, 0xffffffffu));
+        max_deg = std::max(max_deg, d);
+        ++pl.lookup.n_columns;
+        break;
+      }
     }
   }
-  if (pl.info.n_constraints == 0) fail(P3R_EINVAL, "the program has no ASSERT_ZERO");
-  pl.info.max_degree = (uint32_t)std::min<uint64_t>(max_deg, 0xffffffffu);
-  pl.info.log_quotient_degree = air_log_quotient_degree(max_deg);
+  if (lookup) {
+    if (pl.lookup.n_terms == 0) fail(P3R_EINVAL, "the program has no LOOKUP");
+    if (column_open) fail(P3R_EINVAL, "the program ends with a column still open (a LOOKUP_END is missing)");
+    pl.lookup.max_constraint_degree = (uint32_t)std::min<uint64_t>(max_deg, 0xffffffffu);
+  } else {
+    if (pl.info.n_constraints == 0) fail(P3R_EINVAL, "the program has no ASSERT_ZERO");
+    pl.info.max_degree = (uint32_t)std::min<uint64_t>(max_deg, 0xffffffffu);
+    pl.info.log_quotient_degree = air_log_quotient_degree(max_deg);
+  }
 
   // liveness and slots: a linear scan over last uses, one free list per kind, lowest slot first
   using Heap = std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>>;
@@ -165,7 +229,7 @@ inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths
     peak = std::max(peak, ++live);
     if (pl.last_use[i] == i) release((uint32_t)i);   // never read: its slot is free again at once
   }
-  pl.info.peak_live = peak;
+  pl.info.peak_live = pl.lookup.peak_live = peak;
   if (peak > max_live)
     fail(P3R_EUNSUPPORTED, "the program keeps %u values alive at once; P3R_AIR_MAX_LIVE is %u", peak, max_live);
   return pl;
@@ -182,7 +246,11 @@ enum AirDevOp : uint32_t {
   AIR_D_SUB_BB, AIR_D_SUB_EE, AIR_D_SUB_EB, AIR_D_SUB_BE,   // _BE: a base, b extension
   AIR_D_MUL_BB, AIR_D_MUL_EE, AIR_D_MUL_EB,
   AIR_D_NEG_B, AIR_D_NEG_E,
-  AIR_D_ASSERT_B, AIR_D_ASSERT_E                            // acc <- acc * alpha + a
+  AIR_D_ASSERT_B, AIR_D_ASSERT_E,                           // acc <- acc * alpha + a
+  // the lookup seam.  A term m / d joins the open column's fraction num / den: num <- num * d + m * den, den <- den * d
+  // (a = m, b = d; _BE: m base, d extension).  COL_END: f = num / den goes to the output columns a * DC .. and to the row's total
+  AIR_D_TERM_BB, AIR_D_TERM_BE, AIR_D_TERM_EB, AIR_D_TERM_EE,
+  AIR_D_COL_END
 };
 struct AirDevInsn {
   uint32_t op, dst, a, b;   // dst and value operands: LDS words of a lane
@@ -201,10 +269,11 @@ inline AirCompiled air_compile(const AirPlan& pl, const p3r_air_insn* prog, size
   for (size_t m = 0; m < n_mats; ++m) col0[m + 1] = col0[m] + (uint32_t)widths[m];
   AirCompiled out;
   out.insns.reserve(n);
+  uint32_t n_closed = 0;   // lookup columns closed so far
   for (size_t i = 0; i < n; ++i) {
     const p3r_air_insn& in = prog[i];
     AirDevInsn d{};
-    d.dst = in.op == P3R_AIR_ASSERT_ZERO ? 0 : pl.word_of(i, dc);
+    d.dst = air_op_is_sink(in.op) ? 0 : pl.word_of(i, dc);
     const int n_ops = air_op_operands(in.op);
     const bool ea = n_ops >= 1 && pl.is_ext[in.a], eb = n_ops == 2 && pl.is_ext[in.b];
     uint32_t wa = n_ops >= 1 ? pl.word_of(in.a, dc) : 0, wb = n_ops == 2 ? pl.word_of(in.b, dc) : 0;
@@ -232,6 +301,8 @@ inline AirCompiled air_compile(const AirPlan& pl, const p3r_air_insn* prog, size
         break;
       case P3R_AIR_NEG: d.op = ea ? AIR_D_NEG_E : AIR_D_NEG_B; break;
       case P3R_AIR_ASSERT_ZERO: d.op = ea ? AIR_D_ASSERT_E : AIR_D_ASSERT_B; break;
+      case P3R_AIR_LOOKUP: d.op = ea ? (eb ? AIR_D_TERM_EE : AIR_D_TERM_EB) : (eb ? AIR_D_TERM_BE : AIR_D_TERM_BB); break;
+      case P3R_AIR_LOOKUP_END: d.op = AIR_D_COL_END; wa = 1 + n_closed++; break;   // output column 0 is the running sum
     }
     d.a = wa;
     d.b = wb;

@@ -1,16 +1,24 @@
-// The constraint-program interpreter of the quotient seam (p3r_quotient_program_dmat): the caller's AIR, as the
-// instruction stream air_program.h::air_compile made of it, evaluated on every row of the quotient domain of resident
-// LDEs.  The prover's own k_quotient (kernels_stark.hip.h) keeps its constraint systems inlined; this kernel is the
-// same pass with the constraints as data.
+// The program interpreters of the caller's-AIR seams: the instruction stream air_program.h::air_compile made of a
+// p3r_air_insn program, evaluated on every row.
 //
-// One lane per quotient-domain row, in storage (bit-reversed) order, so that the read of a column at the current row is
-// one contiguous run per wave, as in k_quotient; the next row's read is the same run bit-reversal away.  The
-// instruction stream, the column pointers and the constants are read at wave-uniform addresses from read-only buffers
-// (scalar loads), and the dispatch is a wave-uniform branch: no lane ever diverges inside the loop.
+//   k_quotient_program   p3r_quotient_program_dmat: the caller's constraints on every row of the quotient domain of resident
+//                        LDEs.  The prover's own k_quotient (kernels_stark.hip.h) keeps its constraint systems inlined; this
+//                        kernel is the same pass with the constraints as data.
+//   k_logup_program      p3r_logup_program_dmat: the caller's lookups on every row of resident TRACES - the fraction columns
+//                        of the permutation trace and each row's total; the running sum is k_ef_scan's (kernels_stark.hip.h).
+//                        The prover's own k_logup_aux keeps the interactions of the built-in tables inlined.
+//
+// Both are one interpreter, air_step, with the sinks as a template parameter (QuotProgSink / LogupProgSink), as AuxSink /
+// QuotSink share air_interactions for the built-in AIRs.
+//
+// One lane per row: of the quotient domain in storage (bit-reversed) order, of a trace in natural order - either way the
+// read of a column at the current row is one contiguous run per wave; the next row's read is the same run bit-reversal
+// (or one row) away.  The instruction stream, the column pointers and the constants are read at wave-uniform addresses
+// from read-only buffers (scalar loads), and the dispatch is a wave-uniform branch: no lane ever diverges inside the loop.
 //
 // The slot file is LDS, [slot][word][lane]: word w of a lane is slots[w * kAirLanes + lane], so the 64 lanes of an access
 // hit 64 consecutive words - every bank once per 32-lane group, conflict-free - and no register array is indexed by a
-// run-time value (which would put it in scratch memory).  A lane touches its own words only: the kernel has no barrier,
+// run-time value (which would put it in scratch memory).  A lane touches its own words only: the kernels have no barrier,
 // and a lane past the domain's end simply returns.
 //
 // Workgroup = one wave of 64 lanes.  Nothing is shared between lanes, so a larger workgroup buys nothing and only
@@ -43,6 +51,103 @@ struct AirProgArgs {
   uint32_t shift, w_n, g_inv;      // AirDomain's
   uint32_t alpha[kMaxAirDC];
 };
+struct AirLogupArgs {
+  const AirDevInsn* insns;         // n_insns of them
+  const uint32_t* ext_consts;      // Montgomery, DC words per entry
+  const uint32_t* const* cols;     // one pointer per flat column: h words, natural order
+  uint32_t* out;                   // [DC * (1 + G)][h]: the fraction columns are written here, the first DC by k_ef_scan
+  uint32_t* rowsum;                // [DC][h]: sum_g f_g of the row
+  uint32_t* bad_row;               // one word, 0xffffffff before the launch: the smallest row with a zero denominator
+  uint32_t n_insns;
+  int log_h;
+};
+
+// A lane's slot file: word w is s[w * kAirLanes].
+template <class PP, int DC>
+struct AirSlots {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  uint32_t* s;
+  __device__ __forceinline__ F ld(uint32_t w) const { return F::raw(s[w * kAirLanes]); }
+  __device__ __forceinline__ void st(uint32_t w, F v) const { s[w * kAirLanes] = v.v; }
+  __device__ __forceinline__ E lde(uint32_t w) const {
+    E e;
+#pragma unroll
+    for (int k = 0; k < DC; ++k) e.c[k] = F::raw(s[(w + k) * kAirLanes]);
+    return e;
+  }
+  __device__ __forceinline__ void ste(uint32_t w, const E& e) const {
+#pragma unroll
+    for (int k = 0; k < DC; ++k) s[(w + k) * kAirLanes] = e.c[k].v;
+  }
+};
+
+// read-only buffers at wave-uniform addresses; readfirstlane says so where the compiler cannot see it, so that the
+// dispatch is a scalar branch and the slot offsets are scalar
+__device__ __forceinline__ AirDevInsn air_fetch(gptr<const AirDevInsn> insns, uint32_t pc) {
+  AirDevInsn in;
+  in.op = __builtin_amdgcn_readfirstlane(insns[pc].op);
+  in.dst = __builtin_amdgcn_readfirstlane(insns[pc].dst);
+  in.a = __builtin_amdgcn_readfirstlane(insns[pc].a);
+  in.b = __builtin_amdgcn_readfirstlane(insns[pc].b);
+  return in;
+}
+
+// One instruction of a lane whose current / next rows are j / j_next of every column: the value ops here, the rest
+// (selectors, ASSERT_ZERO; lookup terms and column ends) in the sink.
+template <class PP, int DC, class Sink>
+__device__ __forceinline__ void air_step(const AirDevInsn& in, const AirSlots<PP, DC>& sl, gptr<const uint32_t> ext_consts,
+                                         gptr<const uint32_t* const> cols, size_t j, size_t j_next, Sink& sink) {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  uint32_t* s = sl.s;
+  switch (in.op) {
+    case AIR_D_CONST: sl.st(in.dst, F::raw(in.a)); break;
+    case AIR_D_CONST_EXT:
+#pragma unroll
+      for (int k = 0; k < DC; ++k) s[(in.dst + k) * kAirLanes] = ext_consts[in.a + k];
+      break;
+    case AIR_D_LOAD: sl.st(in.dst, F::raw(as_global(cols[in.a])[in.b ? j_next : j])); break;
+    case AIR_D_LOAD_EXT: {
+      const size_t r = in.b ? j_next : j;
+#pragma unroll
+      for (int k = 0; k < DC; ++k) s[(in.dst + k) * kAirLanes] = as_global(cols[in.a + k])[r];
+      break;
+    }
+    case AIR_D_ADD_BB: sl.st(in.dst, sl.ld(in.a) + sl.ld(in.b)); break;
+    case AIR_D_ADD_EE: sl.ste(in.dst, sl.lde(in.a) + sl.lde(in.b)); break;
+    case AIR_D_ADD_EB: { E e = sl.lde(in.a); e.c[0] += sl.ld(in.b); sl.ste(in.dst, e); break; }
+    case AIR_D_SUB_BB: sl.st(in.dst, sl.ld(in.a) - sl.ld(in.b)); break;
+    case AIR_D_SUB_EE: sl.ste(in.dst, sl.lde(in.a) - sl.lde(in.b)); break;
+    case AIR_D_SUB_EB: { E e = sl.lde(in.a); e.c[0] -= sl.ld(in.b); sl.ste(in.dst, e); break; }
+    case AIR_D_SUB_BE: { E e = -sl.lde(in.b); e.c[0] += sl.ld(in.a); sl.ste(in.dst, e); break; }
+    case AIR_D_MUL_BB: sl.st(in.dst, sl.ld(in.a) * sl.ld(in.b)); break;
+    case AIR_D_MUL_EE: sl.ste(in.dst, sl.lde(in.a) * sl.lde(in.b)); break;
+    case AIR_D_MUL_EB: sl.ste(in.dst, sl.lde(in.a) * sl.ld(in.b)); break;
+    case AIR_D_NEG_B: sl.st(in.dst, -sl.ld(in.a)); break;
+    case AIR_D_NEG_E: sl.ste(in.dst, -sl.lde(in.a)); break;
+    default: sink.step(in, sl); break;
+  }
+}
+
+// The sinks of a constraint program: the selectors of the lane's point, and the Horner fold of the asserted values.
+template <class PP, int DC>
+struct QuotProgSink {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  F is_first, is_last, is_transition;
+  E alpha, acc;
+  __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
+    switch (in.op) {
+      case AIR_D_FIRST: sl.st(in.dst, is_first); break;
+      case AIR_D_LAST: sl.st(in.dst, is_last); break;
+      case AIR_D_TRANS: sl.st(in.dst, is_transition); break;
+      case AIR_D_ASSERT_B: acc = acc * alpha; acc.c[0] += sl.ld(in.a); break;
+      case AIR_D_ASSERT_E: acc = acc * alpha + sl.lde(in.a); break;
+      default: break;   // air_compile emits nothing else for a constraint program
+    }
+  }
+};
 
 template <class PP, int DC>
 __global__ void __launch_bounds__(kAirLanes) k_quotient_program(AirProgArgs a) {
@@ -57,84 +162,94 @@ __global__ void __launch_bounds__(kAirLanes) k_quotient_program(AirProgArgs a) {
   const uint32_t c = i & (n_chunks - 1);
   const size_t j_next = bit_reverse((uint32_t)((i + n_chunks) & (n_rows - 1)), a.log_n);
   const gptr<const AirChunkTables> chunks = as_global(a.chunks);
-  F is_first = F::zero(), is_last = F::zero(), is_transition = F::zero();
+  QuotProgSink<PP, DC> sink;
+  sink.is_first = sink.is_last = sink.is_transition = F::zero();
   if (a.flags & 1u) {
     const F x = F::raw(a.shift) * F::raw(a.w_n).pow(i);
-    is_transition = x - F::raw(a.g_inv);
+    sink.is_transition = x - F::raw(a.g_inv);
     if (a.flags & 2u) {
       // x - 1 and x - w_h^-1 are roots of x^h - 1, which has no zero in the domain (air_domain): one shared inversion
       const F xm1 = x - F::one();
-      const F t = (xm1 * is_transition).inv() * F::raw(chunks->zh[c]);
-      is_first = t * is_transition;
-      is_last = t * xm1;
+      const F t = (xm1 * sink.is_transition).inv() * F::raw(chunks->zh[c]);
+      sink.is_first = t * sink.is_transition;
+      sink.is_last = t * xm1;
     }
   }
-  E alpha, acc = E::zero();
+  sink.acc = E::zero();
 #pragma unroll
-  for (int k = 0; k < DC; ++k) alpha.c[k] = F::raw(a.alpha[k]);
+  for (int k = 0; k < DC; ++k) sink.alpha.c[k] = F::raw(a.alpha[k]);
 
-  uint32_t* s = air_slots + threadIdx.x;
-  auto ld = [&](uint32_t w) { return F::raw(s[w * kAirLanes]); };
-  auto st = [&](uint32_t w, F v) { s[w * kAirLanes] = v.v; };
-  auto lde = [&](uint32_t w) {
-    E e;
-#pragma unroll
-    for (int k = 0; k < DC; ++k) e.c[k] = F::raw(s[(w + k) * kAirLanes]);
-    return e;
-  };
-  auto ste = [&](uint32_t w, const E& e) {
-#pragma unroll
-    for (int k = 0; k < DC; ++k) s[(w + k) * kAirLanes] = e.c[k].v;
-  };
-  // read-only buffers at wave-uniform addresses; readfirstlane says so where the compiler cannot see it, so that the
-  // dispatch is a scalar branch and the slot offsets are scalar
+  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
   const gptr<const AirDevInsn> insns = as_global(a.insns);
   const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
   const gptr<const uint32_t* const> cols = as_global(a.cols);
-  for (uint32_t pc = 0; pc < a.n_insns; ++pc) {
-    AirDevInsn in;
-    in.op = __builtin_amdgcn_readfirstlane(insns[pc].op);
-    in.dst = __builtin_amdgcn_readfirstlane(insns[pc].dst);
-    in.a = __builtin_amdgcn_readfirstlane(insns[pc].a);
-    in.b = __builtin_amdgcn_readfirstlane(insns[pc].b);
-    switch (in.op) {
-      case AIR_D_CONST: st(in.dst, F::raw(in.a)); break;
-      case AIR_D_CONST_EXT:
-#pragma unroll
-        for (int k = 0; k < DC; ++k) s[(in.dst + k) * kAirLanes] = ext_consts[in.a + k];
-        break;
-      case AIR_D_LOAD: st(in.dst, F::raw(as_global(cols[in.a])[in.b ? j_next : j])); break;
-      case AIR_D_LOAD_EXT: {
-        const size_t r = in.b ? j_next : j;
-#pragma unroll
-        for (int k = 0; k < DC; ++k) s[(in.dst + k) * kAirLanes] = as_global(cols[in.a + k])[r];
-        break;
-      }
-      case AIR_D_FIRST: st(in.dst, is_first); break;
-      case AIR_D_LAST: st(in.dst, is_last); break;
-      case AIR_D_TRANS: st(in.dst, is_transition); break;
-      case AIR_D_ADD_BB: st(in.dst, ld(in.a) + ld(in.b)); break;
-      case AIR_D_ADD_EE: ste(in.dst, lde(in.a) + lde(in.b)); break;
-      case AIR_D_ADD_EB: { E e = lde(in.a); e.c[0] += ld(in.b); ste(in.dst, e); break; }
-      case AIR_D_SUB_BB: st(in.dst, ld(in.a) - ld(in.b)); break;
-      case AIR_D_SUB_EE: ste(in.dst, lde(in.a) - lde(in.b)); break;
-      case AIR_D_SUB_EB: { E e = lde(in.a); e.c[0] -= ld(in.b); ste(in.dst, e); break; }
-      case AIR_D_SUB_BE: { E e = -lde(in.b); e.c[0] += ld(in.a); ste(in.dst, e); break; }
-      case AIR_D_MUL_BB: st(in.dst, ld(in.a) * ld(in.b)); break;
-      case AIR_D_MUL_EE: ste(in.dst, lde(in.a) * lde(in.b)); break;
-      case AIR_D_MUL_EB: ste(in.dst, lde(in.a) * ld(in.b)); break;
-      case AIR_D_NEG_B: st(in.dst, -ld(in.a)); break;
-      case AIR_D_NEG_E: ste(in.dst, -lde(in.a)); break;
-      case AIR_D_ASSERT_B: acc = acc * alpha; acc.c[0] += ld(in.a); break;
-      case AIR_D_ASSERT_E: acc = acc * alpha + lde(in.a); break;
-      default: break;   // air_compile emits nothing else
-    }
-  }
-  const E quot = acc * F::raw(chunks->zh_inv[c]);
+  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, j, j_next, sink);
+  const E quot = sink.acc * F::raw(chunks->zh_inv[c]);
   const size_t h = n_rows >> a.log_q, r = i >> a.log_q;
   uint32_t* out = chunks->out[c];
 #pragma unroll
   for (int k = 0; k < DC; ++k) as_global(out)[(size_t)k * h + r] = quot.c[k].v;
+}
+
+// The sinks of a lookup program.  The open column's fraction is kept as num / den in registers: a term m / d does
+// num <- num * d + m * den, den <- den * d, and the end of the column the one inversion f = num * den^-1 - one per
+// column, not per term.  f goes to words [col * DC + k][row] of the output (consecutive lanes, consecutive words) and
+// into the row's total.  A lane whose den is zero - upstream divides by zero there - records its row in *bad_row
+// (the smallest wins) and writes zeros; the host refuses the call then (tu_air.hip).
+template <class PP, int DC>
+struct LogupProgSink {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  gptr<uint32_t> out;
+  uint32_t* bad_row;
+  size_t h, row;
+  E num, den, total;
+  __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
+    switch (in.op) {
+      case AIR_D_TERM_BB: { const F m = sl.ld(in.a), d = sl.ld(in.b); num = num * d + den * m; den = den * d; break; }
+      case AIR_D_TERM_BE: { const F m = sl.ld(in.a); const E d = sl.lde(in.b); num = num * d + den * m; den = den * d; break; }
+      case AIR_D_TERM_EB: { const E m = sl.lde(in.a); const F d = sl.ld(in.b); num = num * d + m * den; den = den * d; break; }
+      case AIR_D_TERM_EE: { const E m = sl.lde(in.a), d = sl.lde(in.b); num = num * d + m * den; den = den * d; break; }
+      case AIR_D_COL_END: {
+        E f = E::zero();
+        if (den.is_zero()) atomicMin(bad_row, (uint32_t)row);
+        else f = num * den.inv();
+#pragma unroll
+        for (int k = 0; k < DC; ++k) out[((size_t)in.a * DC + k) * h + row] = f.c[k].v;
+        total += f;
+        num = E::zero();
+        den = E::one();
+        break;
+      }
+      default: break;   // air_compile emits nothing else for a lookup program
+    }
+  }
+};
+
+template <class PP, int DC>
+__global__ void __launch_bounds__(kAirLanes) k_logup_program(AirLogupArgs a) {
+  using E = typename Chal<PP, DC>::type;
+  extern __shared__ uint32_t air_slots[];
+  const size_t h = size_t(1) << a.log_h;
+  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
+  if (r >= h) return;
+  const size_t r_next = (r + 1) & (h - 1);
+  LogupProgSink<PP, DC> sink;
+  sink.out = as_global(a.out);
+  sink.bad_row = a.bad_row;
+  sink.h = h;
+  sink.row = r;
+  sink.num = sink.total = E::zero();
+  sink.den = E::one();
+
+  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
+  const gptr<const AirDevInsn> insns = as_global(a.insns);
+  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
+  const gptr<const uint32_t* const> cols = as_global(a.cols);
+  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
+  const gptr<uint32_t> rowsum = as_global(a.rowsum);
+#pragma unroll
+  for (int k = 0; k < DC; ++k) rowsum[(size_t)k * h + r] = sink.total.c[k].v;
 }
 
 }  // namespace p3r

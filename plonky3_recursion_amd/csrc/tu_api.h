@@ -6,8 +6,8 @@
 // opening seam: it includes open_impl.hip.h, as p3r_core.hip does, for the planner OpenPlan and instantiates the K9
 // kernels of kernels_open.hip.h with the seam's entry point), tu_fri.hip (the reduced openings and the fold at the public
 // FRI seam and the commit-phase leaf view: kernels_fri_points.hip.h, and its own instances of k_fri_inv_points, k_fri_vsum
-// and k_fri_fold), tu_air.hip (the constraint-program seam: the interpreter k_quotient_program of kernels_air.hip.h over the
-// plan and instruction stream of air_program.h),
+// and k_fri_fold), tu_air.hip (the constraint-program and lookup-program seams: the interpreters k_quotient_program and
+// k_logup_program of kernels_air.hip.h over the plan and instruction stream of air_program.h),
 // prep_device.hip.
 // Kernels never call across units; only these host entry points do.
 #pragma once
@@ -116,6 +116,16 @@ std::vector<std::unique_ptr<p3r_dmat>> quotient_program(p3r_ctx* ctx, const p3r_
                                                         const std::vector<const p3r_dmat*>& mats, uint32_t added_bits, uint32_t shift,
                                                         uint32_t log_quotient_degree, const uint32_t* publics, size_t n_public,
                                                         const uint32_t* challenges, size_t n_challenges, const uint32_t* alpha);
+
+// The LogUp gadget for a caller's lookups (tu_air.hip): the lookup program `prog` (p3r_air_insn with P3R_AIR_LOOKUP /
+// P3R_AIR_LOOKUP_END as sinks) evaluated on every row of the traces `mats` (one height h, natural order).  Returns the
+// h x DC * (1 + G) auxiliary trace - the running sum, then one fraction column per closed column - and writes the table's
+// sum to sum_out (host, canonical).  Everything that is refused is refused before anything is allocated or launched, but
+// a zero denominator, which is found on the device: P3R_EINVAL, nothing returned.  Waits for the stream.
+template <class PP>
+std::unique_ptr<p3r_dmat> logup_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
+                                        const uint32_t* publics, size_t n_public, const uint32_t* challenges, size_t n_challenges,
+                                        uint32_t* sum_out);
 
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>

@@ -14,6 +14,7 @@ Names follow the reference's traits where one exists:
   prove_fri             p3_fri::prover::prove_fri (commit phase, final polynomial, query openings) from the calls above
   AirBuilder            p3_uni_stark::SymbolicAirBuilder: an Air::eval recorded as a p3r_air_insn program
   quotient_device       p3_uni_stark::prove's quotient_values + split_evals for that program, on resident LDEs
+  logup_device          p3_lookup's LogUp gadget: the permutation trace and the table's sum for a lookup program, on resident traces
   permute_batch         CryptographicPermutation<[F;16]>::permute over a batch
   generate_trace_rows   Poseidon2CircuitAir::generate_trace_rows (poseidon2-circuit-air/src/air.rs:280)
 """
@@ -255,6 +256,16 @@ class AirBuilder:
     def assert_zero(self, value):
         self._emit(_lib.P3R_AIR_ASSERT_ZERO, value.idx)
 
+    def lookup(self, multiplicity, denominator):
+        """A lookup program's sink: adds the term multiplicity / denominator to the open auxiliary column (and opens one if
+        none is open).  Python ints become constants."""
+        m, d = [v if isinstance(v, AirValue) else self.const(int(v) % self.p) for v in (multiplicity, denominator)]
+        self._emit(_lib.P3R_AIR_LOOKUP, m.idx, d.idx)
+
+    def end_lookup_column(self):
+        """Closes the open auxiliary column of a lookup program."""
+        self._emit(_lib.P3R_AIR_LOOKUP_END)
+
     def program(self):
         """The instructions as an (n, 3) uint32 array of (op, a, b)."""
         return np.array(self.insns, dtype=np.uint32).reshape(-1, 3)
@@ -281,6 +292,21 @@ def air_program_info(cfg, program, widths):
     if rc != 0:
         raise P3rError(rc, lib.p3r_last_error(None).decode())
     return {k: int(getattr(info, k)) for k, _ in _lib.P3rAirInfo._fields_}
+
+
+def lookup_program_info(cfg, program, widths):
+    """p3r_lookup_program_info on the host (no GPU): validates the lookup `program` (an AirBuilder or an (n, 3) array of
+    (op, a, b)) against the matrix `widths` under the field and challenge degree of the p3r_config `cfg`; returns a dict of
+    n_terms, n_columns, max_terms_per_column, max_constraint_degree (the largest degree of a column's constraint: what
+    the quotient must admit) and peak_live.  Raises P3rError with the reason when the program is refused."""
+    lib = _lib.load()
+    arr, n = _air_insns(program)
+    ws = (C.c_size_t * max(1, len(widths)))(*[int(w) for w in widths])
+    info = _lib.P3rLookupInfo()
+    rc = lib.p3r_lookup_program_info(C.byref(cfg), arr, n, ws, len(widths), C.byref(info))
+    if rc != 0:
+        raise P3rError(rc, lib.p3r_last_error(None).decode())
+    return {k: int(getattr(info, k)) for k, _ in _lib.P3rLookupInfo._fields_}
 
 
 class Context:
@@ -579,6 +605,30 @@ class Context:
         self.check(self.lib.p3r_quotient_program_dmat(self.h, arr, n, mats, len(dmats), int(added_bits), 0 if shift is None else int(shift),
                                                       int(log_quotient_degree), pvp, pv.size, chp, len(ch), alp, outs))
         return [DeviceMatrix(self, self.ptr(h)) for h in outs]
+
+    # ---- the caller's lookups: the LogUp permutation trace for a lookup program
+    def lookup_program_info(self, program, widths):
+        """lookup_program_info under this context's field and challenge degree."""
+        return lookup_program_info(self.cfg, program, widths)
+
+    def logup_device(self, program, dmats, public_values=(), challenges=()):
+        """The LogUp auxiliary trace of the lookup `program` (an AirBuilder or an (n, 3) array of (op, a, b), with
+        AirBuilder.lookup / end_lookup_column as its sinks) over the traces `dmats`: one height h, natural row order, not
+        LDEs.  `public_values`: canonical words; `challenges`: (n, DC) canonical words.  Returns (DeviceMatrix, table_sum):
+        the new (h, DC * (1 + G)) matrix holds the running sum s (s[0] = 0, s[r + 1] = s[r] + sum_g f_g[r]) in its first DC
+        columns and the fractions f_g of column g in columns DC * (1 + g) .., the flattening local_ext reads;
+        table_sum is the DC canonical words of s[h - 1] + sum_g f_g[h - 1].  Waits for the device.  A zero denominator
+        raises P3rError (P3R_EINVAL) naming the smallest such row.  The inputs are left as they are."""
+        dc = self.challenge_degree
+        arr, n = _air_insns(program)
+        mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+        pv, pvp = _u32(np.asarray(public_values, dtype=np.uint32).reshape(-1))
+        ch, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
+        total = np.zeros(dc, dtype=np.uint32)
+        out = C.c_void_p()
+        self.check(self.lib.p3r_logup_program_dmat(self.h, arr, n, mats, len(dmats), pvp, pv.size, chp, len(ch), C.byref(out),
+                                                   total.ctypes.data_as(_lib.u32p)))
+        return DeviceMatrix(self, self.ptr(out.value)), total
 
     # ---- the rest of prove_fri: challenger, commit-phase leaf view, final polynomial, schedule, and their composition
     def challenger(self):
