@@ -17,402 +17,21 @@
 // The AIR statements are the ones the quotient kernel evaluates (air_device.hip.h), instantiated
 // over the extension field at zeta.
 #pragma once
-#include <array>
-#include <cstdarg>
 #include <map>
-#include <optional>
-#include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "../../include/p3r.h"
-#include "host_transcript.h"
+#include "proof_grammar.h"
 
 namespace p3r {
-
-struct VerifyFailure : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-[[noreturn]] inline void vfail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  throw VerifyFailure(buf);
-}
-
-// ---- postcard reader (mirror of ProofWriter)
-template <class PP, int DC = 4>
-struct ProofReader {
-  using F = Fp<PP>;
-  using E = typename Chal<PP, DC>::type;
-  const uint8_t* p;
-  const uint8_t* end;
-  bool canonical;
-  uint8_t byte() {
-    if (p >= end) vfail("proof truncated");
-    return *p++;
-  }
-  bool flag() {  // Option / bool tag: postcard admits 0 and 1 only
-    const uint8_t b = byte();
-    if (b > 1) vfail("invalid option tag %u", b);
-    return b != 0;
-  }
-  uint64_t varint() {
-    uint64_t v = 0;
-    for (int shift = 0; shift < 64; shift += 7) {
-      uint8_t b = byte();
-      if (shift == 63 && b > 1) vfail("varint overflows 64 bits");  // postcard: the tenth byte carries one bit
-      v |= (uint64_t)(b & 0x7F) << shift;
-      if (!(b & 0x80)) {
-        if (b == 0 && shift > 0) vfail("non-canonical varint");
-        return v;
-      }
-    }
-    vfail("malformed varint");
-  }
-  size_t len(size_t max) {
-    uint64_t v = varint();
-    if (v > max) vfail("length %llu exceeds the bound %zu", (unsigned long long)v, max);
-    return (size_t)v;
-  }
-  F fe() {
-    uint64_t v = varint();
-    if (v >= PP::P) vfail("field element out of range");
-    return canonical ? F::from_canonical((uint32_t)v) : F::raw((uint32_t)v);
-  }
-  E ef() { E e; for (int i = 0; i < DC; ++i) e.c[i] = fe(); return e; }
-  std::vector<E> vec_ef(size_t max = 1u << 16) {
-    std::vector<E> v(len(max));
-    for (auto& e : v) e = ef();
-    return v;
-  }
-  using Digest = std::array<F, P2_DIGEST>;
-  Digest digest() { Digest d; for (auto& x : d) x = fe(); return d; }
-  std::vector<Digest> cap() {
-    std::vector<Digest> c(len(1u << 16));
-    for (auto& d : c) d = digest();
-    return c;
-  }
-};
-
-template <class PP, int DC = 4>
-struct ParsedProof {
-  using F = Fp<PP>;
-  using E = typename Chal<PP, DC>::type;
-  using Digest = std::array<F, P2_DIGEST>;
-  using Cap = std::vector<Digest>;
-  Cap main_cap, quot_cap;
-  std::optional<Cap> perm_cap, rand_cap;
-  struct Inst {
-    std::vector<E> main_local, prep_local, prep_next, perm_local, perm_next;
-    std::optional<std::vector<E>> main_next, random;
-    std::vector<std::vector<E>> chunks;
-  };
-  // HidingFriPcs::Proof = (OpenedValues<Challenge>, FriProof): rounds -> matrices -> points -> random codeword values
-  std::vector<std::vector<std::vector<std::vector<E>>>> fri_random;
-  std::vector<Inst> insts;
-  std::vector<Cap> commit_caps;
-  std::vector<F> commit_pow;
-  // `salts`: MerkleTreeHidingMmcs - the opening proof is the tuple (per-matrix salts, sibling digests)
-  // (SaltedMmcsProof, recursion/src/pcs/mmcs.rs:763-768); empty under the plain MMCS
-  struct QRound { std::vector<std::vector<F>> rows; std::vector<Digest> path; std::vector<std::vector<F>> salts; };
-  struct QPhase { int la; std::vector<E> sibs; std::vector<Digest> path; std::vector<std::vector<F>> salts; };
-  struct Query { std::vector<QRound> rounds; std::vector<QPhase> phases; };
-  std::vector<Query> queries;
-  std::vector<E> final_poly;
-  F query_pow;
-  std::vector<std::optional<E>> terminals;
-  std::vector<int> degree_bits;
-};
-
-// `consumed`: when given, trailing bytes are allowed and the length of the BatchProof is returned
-// (the outer BatchStarkProof appends its metadata after it, batch_stark_prover.rs:610-636).
-template <class PP, int DC = 4>
-// `zk`: the proof type is the hiding PCS's - a property of the configuration (SC::Pcs in the reference), not of the bytes.
-// `salted`: the MMCSs are hiding ones (p3r_config.mmcs_salt_elems > 0): every opening proof carries its salts first.
-ParsedProof<PP, DC> parse_proof(const uint8_t* bytes, size_t n, bool canonical, size_t* consumed = nullptr,
-                            const ProofLayout& PL = ProofLayout{}, bool zk = false, bool salted = false) {
-  ProofReader<PP, DC> R{bytes, bytes + n, canonical};
-  ParsedProof<PP, DC> P;
-  auto read_commitments = [&] {
-    P.main_cap = R.cap();
-    if (R.flag()) P.perm_cap = R.cap();
-    P.quot_cap = R.cap();
-    if (R.flag()) P.rand_cap = R.cap();
-  };
-  auto read_opened = [&] {
-    P.insts.resize(R.len(64));
-    for (auto& in : P.insts) {
-      for (int f = 0; f < 8; ++f) {
-        switch (PL.opened[f]) {
-          case 0: in.main_local = R.vec_ef(); break;
-          case 1: if (R.flag()) in.main_next = R.vec_ef(); break;
-          case 2: if (!R.flag()) vfail("preprocessed_local missing"); in.prep_local = R.vec_ef(); break;
-          case 3: if (!R.flag()) vfail("preprocessed_next missing"); in.prep_next = R.vec_ef(); break;
-          case 4:
-            in.chunks.resize(R.len(8));
-            for (auto& c : in.chunks) c = R.vec_ef();
-            break;
-          case 5: if (R.flag()) in.random = R.vec_ef(); break;
-          case 6: in.perm_local = R.vec_ef(); break;
-          default: in.perm_next = R.vec_ef(); break;
-        }
-      }
-    }
-  };
-  auto read_queries = [&] {
-    P.queries.resize(R.len(1024));
-    for (auto& q : P.queries) {
-      q.rounds.resize(R.len(8));
-      for (auto& r : q.rounds) {
-        r.rows.resize(R.len(256));
-        for (auto& row : r.rows) {
-          row.resize(R.len(1u << 16));
-          for (auto& x : row) x = R.fe();
-        }
-        if (salted) {
-          r.salts.resize(R.len(256));
-          for (auto& sl : r.salts) { sl.resize(R.len(64)); for (auto& x : sl) x = R.fe(); }
-        }
-        r.path.resize(R.len(64));
-        for (auto& d : r.path) d = R.digest();
-      }
-      q.phases.resize(R.len(64));
-      for (auto& ph : q.phases) {
-        ph.la = R.byte();
-        ph.sibs.resize(R.len(16));
-        for (auto& e : ph.sibs) e = R.ef();
-        if (salted) {
-          ph.salts.resize(R.len(4));
-          for (auto& sl : ph.salts) { sl.resize(R.len(64)); for (auto& x : sl) x = R.fe(); }
-        }
-        ph.path.resize(R.len(64));
-        for (auto& d : ph.path) d = R.digest();
-      }
-    }
-  };
-  auto read_fri = [&] {
-    if (zk) {
-      P.fri_random.resize(R.len(8));
-      for (auto& rd : P.fri_random) {
-        rd.resize(R.len(256));
-        for (auto& m : rd) {
-          m.resize(R.len(2));
-          for (auto& pt : m) pt = R.vec_ef(16);
-        }
-      }
-    }
-    for (int f = 0; f < 5; ++f) {
-      switch (PL.fri[f]) {
-        case 0:
-          P.commit_caps.resize(R.len(64));
-          for (auto& c : P.commit_caps) c = R.cap();
-          break;
-        case 1:
-          P.commit_pow.resize(R.len(64));
-          for (auto& w : P.commit_pow) w = R.fe();
-          break;
-        case 2: read_queries(); break;
-        case 3: P.final_poly = R.vec_ef(); break;
-        default: P.query_pow = R.fe(); break;
-      }
-    }
-  };
-  for (int f = 0; f < 5; ++f) {
-    switch (PL.batch[f]) {
-      case 0: read_commitments(); break;
-      case 1: read_opened(); break;
-      case 2: read_fri(); break;
-      case 3:
-        P.terminals.resize(R.len(64));
-        for (auto& t : P.terminals)
-          if (R.flag()) t = R.ef();
-        break;
-      default:
-        P.degree_bits.resize(R.len(64));
-        for (auto& d : P.degree_bits) d = (int)R.len(40);
-        break;
-    }
-  }
-  if (consumed) *consumed = (size_t)(R.p - bytes);
-  else if (R.p != R.end) vfail("%zu trailing bytes after the proof", (size_t)(R.end - R.p));
-  return P;
-}
-
-// ---- framing-only walk of a BatchProof: what a parent node of the aggregation tree needs before it can
-// hand a child to its verifier circuit (the postcard framing is sound, every field element is in range) -
-// no containers are built.  Runs of field elements take the five-byte fast path (a Montgomery word is
-// >= 2^28 fifteen times out of sixteen): one 8-byte load, one bit-extract, one compare.
-template <class PP>
-struct ProofSkimmer {
-  const uint8_t* p;
-  const uint8_t* end;
-  uint8_t byte() {
-    if (p >= end) vfail("proof truncated");
-    return *p++;
-  }
-  bool flag() {
-    const uint8_t b = byte();
-    if (b > 1) vfail("invalid option tag %u", b);
-    return b != 0;
-  }
-  uint64_t varint() {
-    uint64_t v = 0;
-    for (int shift = 0; shift < 64; shift += 7) {
-      uint8_t b = byte();
-      if (shift == 63 && b > 1) vfail("varint overflows 64 bits");  // postcard: the tenth byte carries one bit
-      v |= (uint64_t)(b & 0x7F) << shift;
-      if (!(b & 0x80)) {
-        if (b == 0 && shift > 0) vfail("non-canonical varint");
-        return v;
-      }
-    }
-    vfail("malformed varint");
-  }
-  size_t len(size_t max) {
-    uint64_t v = varint();
-    if (v > max) vfail("length %llu exceeds the bound %zu", (unsigned long long)v, max);
-    return (size_t)v;
-  }
-  void fes_scalar(size_t k) {
-    for (size_t i = 0; i < k; ++i)
-      if (varint() >= PP::P) vfail("field element out of range");
-  }
-#if defined(P3R_HOST_AVX512)
-  __attribute__((target("bmi2"))) void fes_bmi2(size_t k) {
-    const uint8_t* q = p;
-    size_t i = 0;
-    constexpr uint64_t M = 0x8080808080ull, T = 0x0080808080ull, X = 0x7F7F7F7F7Full;
-    while (i < k) {
-      // four at a time while all four are five-byte words (their positions are then known up front)
-      while (i + 4 <= k && q + 23 <= end) {
-        uint64_t x0, x1, x2, x3;
-        std::memcpy(&x0, q, 8); std::memcpy(&x1, q + 5, 8); std::memcpy(&x2, q + 10, 8); std::memcpy(&x3, q + 15, 8);
-        const bool five = ((x0 & M) == T) & ((x1 & M) == T) & ((x2 & M) == T) & ((x3 & M) == T) &
-                          (((x0 >> 32) & 0x7F) != 0) & (((x1 >> 32) & 0x7F) != 0) & (((x2 >> 32) & 0x7F) != 0) &
-                          (((x3 >> 32) & 0x7F) != 0);
-        if (!five) break;
-        if ((_pext_u64(x0, X) >= PP::P) | (_pext_u64(x1, X) >= PP::P) | (_pext_u64(x2, X) >= PP::P) |
-            (_pext_u64(x3, X) >= PP::P))
-          vfail("field element out of range");
-        q += 20;
-        i += 4;
-      }
-      // a shorter word among the next four (one word in sixteen is below 2^28): one at a time, then retry
-      for (int j = 0; j < 4 && i < k; ++j, ++i) {
-        uint64_t x = 0;
-        if (q + 8 <= end) std::memcpy(&x, q, 8);
-        if ((x & M) == T && ((x >> 32) & 0x7F)) {  // five bytes, canonical
-          if (_pext_u64(x, X) >= PP::P) vfail("field element out of range");
-          q += 5;
-        } else {
-          p = q;
-          if (varint() >= PP::P) vfail("field element out of range");
-          q = p;
-        }
-      }
-    }
-    p = q;
-  }
-#endif
-  void fes(size_t k) {
-#if defined(P3R_HOST_AVX512)
-    static const bool bmi2 = __builtin_cpu_supports("bmi2") && !(getenv("P3R_HOST_SIMD") && getenv("P3R_HOST_SIMD")[0] == '0');
-    if (bmi2) return fes_bmi2(k);
-#endif
-    fes_scalar(k);
-  }
-  int dc = 4;   // words per extension element (the challenge degree)
-  void vec_ef(size_t max = 1u << 16) { fes((size_t)dc * len(max)); }
-  void cap() { fes(P2_DIGEST * len(1u << 16)); }
-};
-
-// Same grammar as parse_proof; returns the length of the BatchProof at the head of `bytes`.
-template <class PP>
-size_t skim_proof(const uint8_t* bytes, size_t n, const ProofLayout& PL = ProofLayout{}, int dc = 4, bool zk = false, bool salted = false) {
-  ProofSkimmer<PP> R{bytes, bytes + n};
-  R.dc = dc;
-  auto opened = [&] {
-    const size_t ni = R.len(64);
-    for (size_t i = 0; i < ni; ++i)
-      for (int f = 0; f < 8; ++f) {
-        switch (PL.opened[f]) {
-          case 0: R.vec_ef(); break;
-          case 1: if (R.flag()) R.vec_ef(); break;
-          case 2: if (!R.flag()) vfail("preprocessed_local missing"); R.vec_ef(); break;
-          case 3: if (!R.flag()) vfail("preprocessed_next missing"); R.vec_ef(); break;
-          case 4: { const size_t nc = R.len(8); for (size_t c = 0; c < nc; ++c) R.vec_ef(); break; }
-          case 5: if (R.flag()) R.vec_ef(); break;
-          default: R.vec_ef(); break;
-        }
-      }
-  };
-  auto queries = [&] {
-    const size_t nq = R.len(1024);
-    for (size_t q = 0; q < nq; ++q) {
-      const size_t nr = R.len(8);
-      for (size_t r = 0; r < nr; ++r) {
-        const size_t rows = R.len(256);
-        for (size_t k = 0; k < rows; ++k) R.fes(R.len(1u << 16));
-        if (salted) { const size_t ns = R.len(256); for (size_t k = 0; k < ns; ++k) R.fes(R.len(64)); }
-        R.fes(P2_DIGEST * R.len(64));
-      }
-      const size_t nph = R.len(64);
-      for (size_t k = 0; k < nph; ++k) {
-        (void)R.byte();
-        R.fes((size_t)dc * R.len(16));
-        if (salted) { const size_t ns = R.len(4); for (size_t k = 0; k < ns; ++k) R.fes(R.len(64)); }
-        R.fes(P2_DIGEST * R.len(64));
-      }
-    }
-  };
-  auto fri = [&] {
-    if (zk) {
-      const size_t nr = R.len(8);
-      for (size_t r = 0; r < nr; ++r) {
-        const size_t nm = R.len(256);
-        for (size_t m = 0; m < nm; ++m) {
-          const size_t np = R.len(2);
-          for (size_t k = 0; k < np; ++k) R.vec_ef(16);
-        }
-      }
-    }
-    for (int f = 0; f < 5; ++f) {
-      switch (PL.fri[f]) {
-        case 0: { const size_t nc = R.len(64); for (size_t c = 0; c < nc; ++c) R.cap(); break; }
-        case 1: R.fes(R.len(64)); break;
-        case 2: queries(); break;
-        case 3: R.vec_ef(); break;
-        default: R.fes(1); break;
-      }
-    }
-  };
-  for (int f = 0; f < 5; ++f) {
-    switch (PL.batch[f]) {
-      case 0:
-        R.cap();
-        if (R.flag()) R.cap();
-        R.cap();
-        if (R.flag()) R.cap();
-        break;
-      case 1: opened(); break;
-      case 2: fri(); break;
-      case 3: { const size_t nt = R.len(64); for (size_t t = 0; t < nt; ++t) if (R.flag()) R.fes(dc); break; }
-      default: { const size_t nd = R.len(64); for (size_t d = 0; d < nd; ++d) (void)R.len(40); break; }
-    }
-  }
-  return (size_t)(R.p - bytes);
-}
 
 // The metadata fields that follow the inner BatchProof (BatchStarkProof, batch_stark_prover.rs:610-636).
 template <class PP>
 void parse_batch_stark_meta(const uint8_t* bytes, size_t len, bool canonical, const ProofLayout& PL, int dc,
                             p3r_batch_stark_meta* M, bool zk = false, bool salted = false) {
   std::memset(M, 0, sizeof *M);
-  M->proof_len = skim_proof<PP>(bytes, len, PL, dc, zk, salted);
-  ProofSkimmer<PP> R{bytes + M->proof_len, bytes + len};
+  ProofChecker<PP> R(bytes, len, dc);
+  M->proof_len = walk_batch_proof(R, PL, zk, salted, true);
   auto u32 = [&](const char* what) {
     const uint64_t v = R.varint();
     if (v > 0xFFFFFFFFull) vfail("%s does not fit 32 bits", what);
@@ -578,6 +197,13 @@ struct ZetaLookupSink {
 };
 
 // ---- MMCS
+// a digest is the first P2_DIGEST words of the permutation state, at either width
+template <class F>
+std::array<F, P2_DIGEST> state_digest(const F* s) {
+  std::array<F, P2_DIGEST> d;
+  std::copy(s, s + P2_DIGEST, d.begin());
+  return d;
+}
 template <class PP>
 std::array<Fp<PP>, P2_DIGEST> sponge_hash(const std::vector<Fp<PP>>& row, const uint32_t* rc) {
   using F = Fp<PP>;
@@ -589,9 +215,7 @@ std::array<Fp<PP>, P2_DIGEST> sponge_hash(const std::vector<Fp<PP>>& row, const 
     for (size_t j = 0; j < (size_t)P2_RATE && g + j < row.size(); ++j) s[j] = row[g + j];
     host_permute<PP>(s, rc);
   }
-  std::array<F, P2_DIGEST> d;
-  for (int k = 0; k < P2_DIGEST; ++k) d[k] = s[k];
-  return d;
+  return state_digest(s);
 }
 template <class PP>
 std::array<Fp<PP>, P2_DIGEST> compress2(const std::array<Fp<PP>, P2_DIGEST>& l, const std::array<Fp<PP>, P2_DIGEST>& r,
@@ -599,9 +223,7 @@ std::array<Fp<PP>, P2_DIGEST> compress2(const std::array<Fp<PP>, P2_DIGEST>& l, 
   Fp<PP> s[P2_WIDTH];
   for (int k = 0; k < P2_DIGEST; ++k) { s[k] = l[k]; s[P2_DIGEST + k] = r[k]; }
   host_permute<PP>(s, rc);
-  std::array<Fp<PP>, P2_DIGEST> d;
-  for (int k = 0; k < P2_DIGEST; ++k) d[k] = s[k];
-  return d;
+  return state_digest(s);
 }
 
 // verify_batch of one commitment: `log_heights[m]` / rows[m] in COMMIT order; index addresses the
@@ -652,9 +274,7 @@ std::array<Fp<PP>, P2_DIGEST> sponge_hash_w32(const std::vector<Fp<PP>>& row, co
     for (size_t j = 0; j < 24 && g + j < row.size(); ++j) s[j] = row[g + j];
     p2w_permute_traced<PP>(s, rcw, sink);
   }
-  std::array<F, P2_DIGEST> d;
-  for (int k = 0; k < P2_DIGEST; ++k) d[k] = s[k];
-  return d;
+  return state_digest(s);
 }
 template <class PP>
 std::array<Fp<PP>, P2_DIGEST> compress4(const std::array<Fp<PP>, P2_DIGEST>* c, const uint32_t* rcw) {
@@ -664,9 +284,7 @@ std::array<Fp<PP>, P2_DIGEST> compress4(const std::array<Fp<PP>, P2_DIGEST>* c, 
     for (int k = 0; k < P2_DIGEST; ++k) s[j * P2_DIGEST + k] = c[j][k];
   struct { void put(F) {} } sink;
   p2w_permute_traced<PP>(s, rcw, sink);
-  std::array<F, P2_DIGEST> d;
-  for (int k = 0; k < P2_DIGEST; ++k) d[k] = s[k];
-  return d;
+  return state_digest(s);
 }
 template <class PP>
 void mmcs_verify4(const std::vector<std::array<Fp<PP>, P2_DIGEST>>& cap, int cap_height, const std::vector<int>& log_heights,
@@ -845,175 +463,225 @@ std::vector<std::vector<F>> salted_rows(const std::vector<std::vector<F>>& rows,
   return out;
 }
 
+// One MMCS as a verifier sees it.  `rc`: the permutation constants in Montgomery form, the width-16 round constants
+// followed by the width-32 table (poseidon2.h; csrc/p3r_core.hip::constants_table).
+template <class PP>
+struct MmcsChecker {
+  using F = Fp<PP>;
+  using Digest = std::array<F, P2_DIGEST>;
+  int arity, salt_elems;
+  const uint32_t* rc;
+  // Mmcs::verify_batch of one opening: salt the rows, then the walk of the configured arity over its own constants
+  void check_opening(const std::vector<Digest>& cap, int cap_height, const std::vector<int>& log_heights,
+                     const std::vector<std::vector<F>>& rows, const std::vector<std::vector<F>>& salts, size_t index,
+                     const std::vector<Digest>& path, const char* what) const {
+    const auto leaf_rows = salted_rows<F>(rows, salts, salt_elems, what);
+    if (arity == 4) mmcs_verify4<PP>(cap, cap_height, log_heights, leaf_rows, index, path, rc + p2_num_constants<PP>(), what);
+    else mmcs_verify<PP>(cap, cap_height, log_heights, leaf_rows, index, path, rc, what);
+  }
+};
+
+template <class PP>
+std::vector<uint32_t> montgomery_constants(const std::vector<uint32_t>& rc_canonical) {
+  if (rc_canonical.size() != (size_t)p2_num_constants<PP>() + (size_t)p2w_num_constants<PP>()) vfail("wrong number of permutation constants");
+  std::vector<uint32_t> rc(rc_canonical.size());
+  for (size_t i = 0; i < rc.size(); ++i) rc[i] = Fp<PP>::from_canonical(rc_canonical[i]).v;
+  return rc;
+}
+
+// The verifier's state and its phases, named after prove_batch's (prove_impl.hip.h): the members are what crosses a
+// phase boundary, everything else is a local of its phase.
 template <class PP, int DC = 4>
-void verify_batch(const VerifyParams& prm, const std::vector<uint32_t>& rc_canonical, const std::vector<AirParams>& airs,
-                  const std::vector<uint32_t>& prep_cap_canonical, const std::vector<uint32_t>& expected_degree_bits,
-                  const uint8_t* bytes, size_t n_bytes, bool canonical) {
+struct BatchVerifier {
   using F = Fp<PP>;
   using E = typename Chal<PP, DC>::type;
   using Digest = std::array<F, P2_DIGEST>;
-  const int zk = prm.zk ? 1 : 0, R = zk ? prm.num_random_codewords : 0;
-  if (zk && (R < 1 || R > 8)) vfail("num_random_codewords must be in 1..8");
-  if (prm.mmcs_salt_elems < 0 || prm.mmcs_salt_elems > 16) vfail("mmcs_salt_elems must be in 0..16");
-  const ParsedProof<PP, DC> P = parse_proof<PP, DC>(bytes, n_bytes, canonical, nullptr, prm.layout, zk != 0, prm.mmcs_salt_elems != 0);
-  const size_t ni = airs.size();
-  // the width-16 round constants, followed by the width-32 table (poseidon2.h; csrc/p3r_core.hip::constants_table)
-  if (rc_canonical.size() != (size_t)p2_num_constants<PP>() + (size_t)p2w_num_constants<PP>()) vfail("wrong number of permutation constants");
-  std::vector<uint32_t> rc(rc_canonical.size());
-  for (size_t i = 0; i < rc.size(); ++i) rc[i] = F::from_canonical(rc_canonical[i]).v;
-  const int p2w = p2_perm_cols<PP>() + 2;
-  if (P.insts.size() != ni || P.degree_bits.size() != ni || P.terminals.size() != ni)
-    vfail("proof has %zu instances, the verifier was given %zu AIRs", P.insts.size(), ni);
-  const int cap_h = prm.cap_height, lb = prm.log_blowup;
-  std::vector<Digest> prep_cap(size_t(1) << cap_h);
-  if (prep_cap_canonical.size() != prep_cap.size() * P2_DIGEST) vfail("preprocessed commitment has the wrong size");
-  for (size_t j = 0; j < prep_cap.size(); ++j)
-    for (int k = 0; k < P2_DIGEST; ++k) prep_cap[j][k] = F::from_canonical(prep_cap_canonical[j * P2_DIGEST + k]);
+  // a committed matrix of an input batch: log LDE height, width, opening points and the values claimed there
+  struct Mat { int log_h; int w; std::vector<E> z; std::vector<std::vector<E>> vals; };
 
-  // ---- shapes
-  // randomisation must match the PCS's ZK setting (batch_stark.rs:424-428: RandomizationError)
-  if (P.rand_cap.has_value() != (zk != 0)) vfail("RandomizationError: random commitment presence does not match the ZK setting");
-  for (auto& in : P.insts)
-    if (in.random.has_value() != (zk != 0)) vfail("RandomizationError: random opened values presence does not match the ZK setting");
-  std::vector<LookupLayout> layouts(ni);
-  std::vector<int> log_n(ni), log_e(ni), width(ni), prep_w(ni);   // base / extended (committed) degree bits
-  bool any_lookup = false;
-  std::vector<int> perm_insts;
-  for (size_t i = 0; i < ni; ++i) {
-    const auto& in = P.insts[i];
-    layouts[i] = lookup_layout(airs[i], zk);
-    log_e[i] = P.degree_bits[i];
-    // the domains are the verifier's, not the prover's: recursion/src/verifier/batch_stark.rs:793 (ZK: the preprocessed
-    // metadata holds the EXTENDED degree bits, recursion.rs:374)
-    if (expected_degree_bits.size() != ni || (uint32_t)log_e[i] != expected_degree_bits[i])
-      vfail("InvalidProofShape: instance %zu declares degree_bits %d, the preprocessed metadata has %u", i, log_e[i],
-            i < expected_degree_bits.size() ? expected_degree_bits[i] : 0u);
-    if (log_e[i] < zk) vfail("InvalidProofShape: extended degree bits smaller than the ZK adjustment");   // :536
-    log_n[i] = log_e[i] - zk;
-    if (log_e[i] + lb > PP::TWO_ADICITY) vfail("instance %zu: degree too large", i);
-    width[i] = air_width_of(airs[i], p2w, p2w_perm_cols<PP>() + 4);
-    prep_w[i] = air_prep_width_of(airs[i]);
-    // quotient_degree = 1 << (log_qd + is_zk) (:487-496)
-    const size_t aw = (size_t)layouts[i].aux_width() * DC, C = size_t(1) << (layouts[i].log_chunks + zk);
-    if (in.random && in.random->size() != (size_t)DC) vfail("RandomizationError: instance %zu: %zu random opened values", i, in.random->size());
-    if (in.main_local.size() != (size_t)width[i]) vfail("instance %zu: %zu main openings, the AIR has %d columns", i, in.main_local.size(), width[i]);
-    if (air_uses_next(airs[i]) != in.main_next.has_value()) vfail("instance %zu: main next-row openings do not match the AIR", i);
-    if (in.main_next && in.main_next->size() != (size_t)width[i]) vfail("instance %zu: bad main next width", i);
-    if (in.prep_local.size() != (size_t)prep_w[i] || in.prep_next.size() != (size_t)prep_w[i]) vfail("instance %zu: bad preprocessed opening width", i);
-    if (in.perm_local.size() != aw || in.perm_next.size() != aw) vfail("instance %zu: bad permutation opening width", i);
-    if (in.chunks.size() != C) vfail("instance %zu: %zu quotient chunks, expected %zu", i, in.chunks.size(), C);
-    for (auto& c : in.chunks) if (c.size() != (size_t)DC) vfail("instance %zu: bad quotient chunk width", i);
-    if ((layouts[i].n_groups > 0) != P.terminals[i].has_value()) vfail("instance %zu: lookup terminal presence mismatch", i);
-    if (layouts[i].n_groups) { any_lookup = true; perm_insts.push_back((int)i); }
-  }
-  if (any_lookup != P.perm_cap.has_value()) vfail("permutation commitment presence mismatch");
+  const VerifyParams& prm;
+  const std::vector<AirParams>& airs;
+  const size_t ni;
+  const int zk, R, lb, cap_h;
+  const ParsedProof<PP, DC> P;
+  const std::vector<uint32_t> rc;
+  const MmcsChecker<PP> mmcs;
+  std::vector<Digest> prep_cap;
+  std::vector<LookupLayout> layouts;
+  std::vector<int> log_n, log_e, width, prep_w;   // base / extended (committed) degree bits
+  std::vector<int> perm_insts;                    // the instances with lookups
+  HostChallenger<PP, DC> ch;
+  E alpha, zeta, l_prefix = E::zero(), l_beta_pow[kMaxExtD + 1];
+  std::vector<std::vector<Mat>> rounds;
+  std::vector<const std::vector<Digest>*> round_caps;
+  std::vector<int> las;
+  std::vector<E> betas, fa_pow;
+  int log_max = 0;
 
-  // ---- transcript (same order as prove_batch)
-  HostChallenger<PP, DC> ch(rc.data());
-  auto observe_cap = [&](const std::vector<Digest>& cap) { for (auto& d : cap) for (auto x : d) ch.observe(x); };
-  ch.observe_base_as_ext(ni);
-  for (size_t i = 0; i < ni; ++i) {
-    ch.observe_base_as_ext(log_e[i]);
-    ch.observe_base_as_ext(log_n[i]);
-    ch.observe_base_as_ext(width[i]);
-    ch.observe_base_as_ext(uint64_t(1) << (layouts[i].log_chunks + zk));
+  BatchVerifier(const VerifyParams& prm_, const std::vector<uint32_t>& rc_canonical, const std::vector<AirParams>& airs_,
+                const std::vector<uint32_t>& prep_cap_canonical, const uint8_t* bytes, size_t n_bytes, bool canonical)
+      : prm(prm_), airs(airs_), ni(airs_.size()), zk(prm_.zk ? 1 : 0), R(zk ? prm_.num_random_codewords : 0), lb(prm_.log_blowup),
+        cap_h(prm_.cap_height), P(parse(prm_, bytes, n_bytes, canonical)), rc(montgomery_constants<PP>(rc_canonical)),
+        mmcs{prm_.mmcs_arity, prm_.mmcs_salt_elems, rc.data()}, prep_cap(size_t(1) << cap_h), ch(rc.data()) {
+    if (P.insts.size() != ni || P.degree_bits.size() != ni || P.terminals.size() != ni)
+      vfail("proof has %zu instances, the verifier was given %zu AIRs", P.insts.size(), ni);
+    if (prep_cap_canonical.size() != prep_cap.size() * P2_DIGEST) vfail("preprocessed commitment has the wrong size");
+    for (size_t j = 0; j < prep_cap.size(); ++j)
+      for (int k = 0; k < P2_DIGEST; ++k) prep_cap[j][k] = F::from_canonical(prep_cap_canonical[j * P2_DIGEST + k]);
+    for (auto& b : l_beta_pow) b = E::zero();
   }
-  observe_cap(P.main_cap);
-  for (size_t i = 0; i < ni; ++i) ch.observe_base_as_ext(prep_w[i]);
-  observe_cap(prep_cap);
-  E l_prefix = E::zero(), l_beta_pow[kMaxExtD + 1];
-  for (auto& b : l_beta_pow) b = E::zero();
-  if (any_lookup) {
-    const E alpha_l = ch.sample_ext(), beta_l = ch.sample_ext();
-    E bp = E::one();
-    // gamma = beta^W, W = the widest bus tuple = 1 + circuit extension degree (get_perm_challenges,
-    // recursion/src/verifier/batch_stark.rs:1086-1100)
-    int tuple_w = 2;
-    for (auto& a : airs) tuple_w = std::max(tuple_w, std::min(a.ext_d, kMaxExtD) + 1);
-    for (int j = 0; j < tuple_w; ++j) { l_beta_pow[j] = bp; bp *= beta_l; }
-    l_prefix = alpha_l + bp;
-    observe_cap(*P.perm_cap);
-    for (int i : perm_insts) ch.observe_ext(*P.terminals[i]);
+  static ParsedProof<PP, DC> parse(const VerifyParams& prm, const uint8_t* bytes, size_t n_bytes, bool canonical) {
+    ProofBuilder<PP, DC> B(bytes, n_bytes, canonical);
+    walk_batch_proof(B, prm.layout, prm.zk != 0, prm.mmcs_salt_elems != 0, false);
+    return std::move(B.P);
   }
-  const E alpha = ch.sample_ext();
-  observe_cap(P.quot_cap);
-  if (zk) observe_cap(*P.rand_cap);   // :623-625
-  const E zeta = ch.sample_ext();
+  bool any_lookup() const { return !perm_insts.empty(); }
+  void observe_cap(const std::vector<Digest>& cap) { for (auto& d : cap) for (auto x : d) ch.observe(x); }
+
+  void shapes(const std::vector<uint32_t>& expected_degree_bits) {
+    // randomisation must match the PCS's ZK setting (batch_stark.rs:424-428: RandomizationError)
+    if (P.rand_cap.has_value() != (zk != 0)) vfail("RandomizationError: random commitment presence does not match the ZK setting");
+    for (auto& in : P.insts)
+      if (in.random.has_value() != (zk != 0)) vfail("RandomizationError: random opened values presence does not match the ZK setting");
+    layouts.resize(ni); log_n.resize(ni); log_e.resize(ni); width.resize(ni); prep_w.resize(ni);
+    const int p2w = p2_perm_cols<PP>() + 2;
+    for (size_t i = 0; i < ni; ++i) {
+      const auto& in = P.insts[i];
+      layouts[i] = lookup_layout(airs[i], zk);
+      log_e[i] = P.degree_bits[i];
+      // the domains are the verifier's, not the prover's: recursion/src/verifier/batch_stark.rs:793 (ZK: the preprocessed
+      // metadata holds the EXTENDED degree bits, recursion.rs:374)
+      if (expected_degree_bits.size() != ni || (uint32_t)log_e[i] != expected_degree_bits[i])
+        vfail("InvalidProofShape: instance %zu declares degree_bits %d, the preprocessed metadata has %u", i, log_e[i],
+              i < expected_degree_bits.size() ? expected_degree_bits[i] : 0u);
+      if (log_e[i] < zk) vfail("InvalidProofShape: extended degree bits smaller than the ZK adjustment");   // :536
+      log_n[i] = log_e[i] - zk;
+      if (log_e[i] + lb > PP::TWO_ADICITY) vfail("instance %zu: degree too large", i);
+      width[i] = air_width_of(airs[i], p2w, p2w_perm_cols<PP>() + 4);
+      prep_w[i] = air_prep_width_of(airs[i]);
+      // quotient_degree = 1 << (log_qd + is_zk) (:487-496)
+      const size_t aw = (size_t)layouts[i].aux_width() * DC, C = size_t(1) << (layouts[i].log_chunks + zk);
+      if (in.random && in.random->size() != (size_t)DC) vfail("RandomizationError: instance %zu: %zu random opened values", i, in.random->size());
+      if (in.main_local.size() != (size_t)width[i]) vfail("instance %zu: %zu main openings, the AIR has %d columns", i, in.main_local.size(), width[i]);
+      if (air_uses_next(airs[i]) != in.main_next.has_value()) vfail("instance %zu: main next-row openings do not match the AIR", i);
+      if (in.main_next && in.main_next->size() != (size_t)width[i]) vfail("instance %zu: bad main next width", i);
+      if (in.prep_local.size() != (size_t)prep_w[i] || in.prep_next.size() != (size_t)prep_w[i]) vfail("instance %zu: bad preprocessed opening width", i);
+      if (in.perm_local.size() != aw || in.perm_next.size() != aw) vfail("instance %zu: bad permutation opening width", i);
+      if (in.chunks.size() != C) vfail("instance %zu: %zu quotient chunks, expected %zu", i, in.chunks.size(), C);
+      for (auto& c : in.chunks) if (c.size() != (size_t)DC) vfail("instance %zu: bad quotient chunk width", i);
+      if ((layouts[i].n_groups > 0) != P.terminals[i].has_value()) vfail("instance %zu: lookup terminal presence mismatch", i);
+      if (layouts[i].n_groups) perm_insts.push_back((int)i);
+    }
+    if (any_lookup() != P.perm_cap.has_value()) vfail("permutation commitment presence mismatch");
+  }
+
+  // same order as prove_batch: instance shapes, main and preprocessed commitments, the lookup challenges, alpha, zeta
+  void transcript_head() {
+    ch.observe_base_as_ext(ni);
+    for (size_t i = 0; i < ni; ++i) {
+      ch.observe_base_as_ext(log_e[i]);
+      ch.observe_base_as_ext(log_n[i]);
+      ch.observe_base_as_ext(width[i]);
+      ch.observe_base_as_ext(uint64_t(1) << (layouts[i].log_chunks + zk));
+    }
+    observe_cap(P.main_cap);
+    for (size_t i = 0; i < ni; ++i) ch.observe_base_as_ext(prep_w[i]);
+    observe_cap(prep_cap);
+    if (any_lookup()) {
+      const E alpha_l = ch.sample_ext(), beta_l = ch.sample_ext();
+      E bp = E::one();
+      // gamma = beta^W, W = the widest bus tuple = 1 + circuit extension degree (get_perm_challenges,
+      // recursion/src/verifier/batch_stark.rs:1086-1100)
+      int tuple_w = 2;
+      for (auto& a : airs) tuple_w = std::max(tuple_w, std::min(a.ext_d, kMaxExtD) + 1);
+      for (int j = 0; j < tuple_w; ++j) { l_beta_pow[j] = bp; bp *= beta_l; }
+      l_prefix = alpha_l + bp;
+      observe_cap(*P.perm_cap);
+      for (int i : perm_insts) ch.observe_ext(*P.terminals[i]);
+    }
+    alpha = ch.sample_ext();
+    observe_cap(P.quot_cap);
+    if (zk) observe_cap(*P.rand_cap);   // :623-625
+    zeta = ch.sample_ext();
+  }
+
   // input batches in round order ([random,] main, quotient, preprocessed, permutation): matrices (log LDE height,
   // width), points and claimed values.  ZK: every committed matrix has R more columns - the random codewords - whose
   // values at each point are the opening proof's first item; they are appended to the point's values before anything
   // is observed or reduced (merge_hiding_random_openings, pcs/fri/targets.rs:1076-1130; batch_stark.rs:1116-1260).
-  struct Mat { int log_h; int w; std::vector<E> z; std::vector<std::vector<E>> vals; };
-  std::vector<std::vector<Mat>> rounds;
-  if (zk) {
+  void opening_rounds() {
+    if (zk) {
+      rounds.emplace_back();
+      round_caps.push_back(&*P.rand_cap);
+      for (size_t i = 0; i < ni; ++i) rounds.back().push_back({log_e[i] + lb, DC, {zeta}, {*P.insts[i].random}});   // :645-661
+    }
     rounds.emplace_back();
-    for (size_t i = 0; i < ni; ++i) rounds.back().push_back({log_e[i] + lb, DC, {zeta}, {*P.insts[i].random}});   // :645-661
-  }
-  rounds.emplace_back();
-  for (size_t i = 0; i < ni; ++i) {
-    Mat m{log_e[i] + lb, width[i], {zeta}, {P.insts[i].main_local}};
-    // zeta * g of the BASE trace domain (:663-700)
-    if (P.insts[i].main_next) { m.z.push_back(zeta * F::two_adic_generator(log_n[i])); m.vals.push_back(*P.insts[i].main_next); }
-    rounds.back().push_back(m);
-  }
-  rounds.emplace_back();
-  for (size_t i = 0; i < ni; ++i)   // randomized_quotient_domains: natural_domain_for_degree(size << is_zk) (:719-727)
-    for (auto& c : P.insts[i].chunks) rounds.back().push_back({log_e[i] + lb, DC, {zeta}, {c}});
-  rounds.emplace_back();
-  for (size_t i = 0; i < ni; ++i)
-    rounds.back().push_back({log_e[i] + lb, prep_w[i], {zeta, zeta * F::two_adic_generator(log_n[i])},
-                             {P.insts[i].prep_local, P.insts[i].prep_next}});
-  if (any_lookup) {
+    round_caps.push_back(&P.main_cap);
+    for (size_t i = 0; i < ni; ++i) {
+      Mat m{log_e[i] + lb, width[i], {zeta}, {P.insts[i].main_local}};
+      // zeta * g of the BASE trace domain (:663-700)
+      if (P.insts[i].main_next) { m.z.push_back(zeta * F::two_adic_generator(log_n[i])); m.vals.push_back(*P.insts[i].main_next); }
+      rounds.back().push_back(m);
+    }
     rounds.emplace_back();
-    for (int i : perm_insts)
-      rounds.back().push_back({log_e[i] + lb, layouts[i].aux_width() * DC, {zeta, zeta * F::two_adic_generator(log_n[i])},
-                               {P.insts[i].perm_local, P.insts[i].perm_next}});
-  }
-  if (zk) {
-    if (P.fri_random.size() != rounds.size()) vfail("InvalidProofShape: hiding FRI proof: random rounds count does not match commitments");
-    for (size_t r = 0; r < rounds.size(); ++r) {
-      if (P.fri_random[r].size() != rounds[r].size()) vfail("InvalidProofShape: hiding FRI proof: random matrices count does not match (round %zu)", r);
-      for (size_t m = 0; m < rounds[r].size(); ++m) {
-        Mat& M = rounds[r][m];
-        if (P.fri_random[r][m].size() != M.z.size()) vfail("InvalidProofShape: hiding FRI proof: random points count does not match (round %zu matrix %zu)", r, m);
-        for (size_t p = 0; p < M.z.size(); ++p) {
-          const auto& extra = P.fri_random[r][m][p];
-          if (extra.size() != (size_t)R) vfail("InvalidProofShape: hiding FRI proof: %zu random codeword values, expected %d", extra.size(), R);
-          M.vals[p].insert(M.vals[p].end(), extra.begin(), extra.end());
+    round_caps.push_back(&P.quot_cap);
+    for (size_t i = 0; i < ni; ++i)   // randomized_quotient_domains: natural_domain_for_degree(size << is_zk) (:719-727)
+      for (auto& c : P.insts[i].chunks) rounds.back().push_back({log_e[i] + lb, DC, {zeta}, {c}});
+    rounds.emplace_back();
+    round_caps.push_back(&prep_cap);
+    for (size_t i = 0; i < ni; ++i)
+      rounds.back().push_back({log_e[i] + lb, prep_w[i], {zeta, zeta * F::two_adic_generator(log_n[i])},
+                               {P.insts[i].prep_local, P.insts[i].prep_next}});
+    if (any_lookup()) {
+      rounds.emplace_back();
+      round_caps.push_back(&*P.perm_cap);
+      for (int i : perm_insts)
+        rounds.back().push_back({log_e[i] + lb, layouts[i].aux_width() * DC, {zeta, zeta * F::two_adic_generator(log_n[i])},
+                                 {P.insts[i].perm_local, P.insts[i].perm_next}});
+    }
+    if (zk) {
+      if (P.fri_random.size() != rounds.size()) vfail("InvalidProofShape: hiding FRI proof: random rounds count does not match commitments");
+      for (size_t r = 0; r < rounds.size(); ++r) {
+        if (P.fri_random[r].size() != rounds[r].size()) vfail("InvalidProofShape: hiding FRI proof: random matrices count does not match (round %zu)", r);
+        for (size_t m = 0; m < rounds[r].size(); ++m) {
+          Mat& M = rounds[r][m];
+          if (P.fri_random[r][m].size() != M.z.size()) vfail("InvalidProofShape: hiding FRI proof: random points count does not match (round %zu matrix %zu)", r, m);
+          for (size_t p = 0; p < M.z.size(); ++p) {
+            const auto& extra = P.fri_random[r][m][p];
+            if (extra.size() != (size_t)R) vfail("InvalidProofShape: hiding FRI proof: %zu random codeword values, expected %d", extra.size(), R);
+            M.vals[p].insert(M.vals[p].end(), extra.begin(), extra.end());
+          }
+          M.w += R;
         }
-        M.w += R;
       }
     }
+    for (auto& r : rounds) for (auto& m : r) for (auto& pv : m.vals) for (auto& v : pv) ch.observe_ext(v);
   }
-  for (auto& r : rounds) for (auto& m : r) for (auto& pv : m.vals) for (auto& v : pv) ch.observe_ext(v);
 
-  // ---- constraints at zeta
-  const F gen = F::generator();
-  E terminal_sum = E::zero();
-  for (size_t i = 0; i < ni; ++i) {
-    const auto& in = P.insts[i];
-    ZetaInstance<PP, DC> zi{&in.main_local, in.main_next ? &*in.main_next : nullptr, &in.prep_local, &in.prep_next,
-                        &in.perm_local, &in.perm_next, &in.chunks, P.terminals[i] ? &*P.terminals[i] : nullptr};
-    check_instance_at_zeta<PP, DC>(airs[i], layouts[i], log_n[i], zi, alpha, zeta, l_prefix, l_beta_pow, rc.data(), i, zk);
-    if (layouts[i].n_groups) terminal_sum += *P.terminals[i];
+  void constraints_at_zeta() {
+    E terminal_sum = E::zero();
+    for (size_t i = 0; i < ni; ++i) {
+      const auto& in = P.insts[i];
+      ZetaInstance<PP, DC> zi{&in.main_local, in.main_next ? &*in.main_next : nullptr, &in.prep_local, &in.prep_next,
+                          &in.perm_local, &in.perm_next, &in.chunks, P.terminals[i] ? &*P.terminals[i] : nullptr};
+      check_instance_at_zeta<PP, DC>(airs[i], layouts[i], log_n[i], zi, alpha, zeta, l_prefix, l_beta_pow, rc.data(), i, zk);
+      if (layouts[i].n_groups) terminal_sum += *P.terminals[i];
+    }
+    if (any_lookup() && !terminal_sum.is_zero()) vfail("global lookup sum is not zero");
   }
-  if (any_lookup && !terminal_sum.is_zero()) vfail("global lookup sum is not zero");
 
-  // ---- FRI transcript
-  const E fri_alpha = ch.sample_ext();
-  std::vector<const std::vector<Digest>*> round_caps;
-  if (zk) round_caps.push_back(&*P.rand_cap);
-  round_caps.push_back(&P.main_cap); round_caps.push_back(&P.quot_cap); round_caps.push_back(&prep_cap);
-  if (any_lookup) round_caps.push_back(&*P.perm_cap);
-  int log_max = 0;
-  std::vector<int> heights;
-  for (auto& r : rounds) for (auto& m : r) { log_max = std::max(log_max, m.log_h); heights.push_back(m.log_h); }
-  std::sort(heights.rbegin(), heights.rend());
-  heights.erase(std::unique(heights.begin(), heights.end()), heights.end());
-  const int log_final = prm.log_final_poly_len + lb;
-  // the arity schedule the prover must have used (the FRI prover's rule, prove_impl.hip.h step 7)
-  std::vector<int> las;
-  {
+  // the FRI transcript: the arity schedule the prover must have used (the FRI prover's rule, prove_impl.hip.h step 7),
+  // the commit caps with their proofs of work and betas, the final polynomial, the query proof of work
+  void fri_commit_phase() {
+    const E fri_alpha = ch.sample_ext();
+    size_t max_w = 1;
+    std::vector<int> heights;
+    for (auto& r : rounds) for (auto& m : r) { log_max = std::max(log_max, m.log_h); heights.push_back(m.log_h); max_w = std::max(max_w, (size_t)m.w); }
+    fa_pow.assign(max_w + 1, E::one());
+    for (size_t c = 1; c <= max_w; ++c) fa_pow[c] = fa_pow[c - 1] * fri_alpha;
+    std::sort(heights.rbegin(), heights.rend());
+    heights.erase(std::unique(heights.begin(), heights.end()), heights.end());
+    const int log_final = prm.log_final_poly_len + lb;
     size_t next_h = 1;
     int cur = log_max;
     while (cur > log_final) {
@@ -1026,32 +694,34 @@ void verify_batch(const VerifyParams& prm, const std::vector<uint32_t>& rc_canon
     }
     if (next_h != heights.size()) vfail("FRI: an input height is never rolled in");
     if (cur != log_final) vfail("FRI: fold schedule does not end at the final polynomial length");
+    if (P.commit_caps.size() != las.size() || P.commit_pow.size() != las.size()) vfail("FRI: %zu commit phases, expected %zu", P.commit_caps.size(), las.size());
+    if (P.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) vfail("FRI: final polynomial has the wrong length");
+    for (size_t p = 0; p < las.size(); ++p) {
+      observe_cap(P.commit_caps[p]);
+      if (!ch.check_witness(prm.commit_pow_bits, P.commit_pow[p])) vfail("FRI: invalid commit-phase proof of work");
+      betas.push_back(ch.sample_ext());
+    }
+    for (auto& c : P.final_poly) ch.observe_ext(c);
+    for (int la : las) ch.observe(F::from_canonical((uint32_t)la));
+    if (!ch.check_witness(prm.query_pow_bits, P.query_pow)) vfail("FRI: invalid query proof of work");
+    if ((int)P.queries.size() != prm.num_queries) vfail("FRI: %zu queries, expected %d", P.queries.size(), prm.num_queries);
   }
-  if (P.commit_caps.size() != las.size() || P.commit_pow.size() != las.size()) vfail("FRI: %zu commit phases, expected %zu", P.commit_caps.size(), las.size());
-  if (P.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) vfail("FRI: final polynomial has the wrong length");
-  std::vector<E> betas;
-  for (size_t p = 0; p < las.size(); ++p) {
-    observe_cap(P.commit_caps[p]);
-    if (!ch.check_witness(prm.commit_pow_bits, P.commit_pow[p])) vfail("FRI: invalid commit-phase proof of work");
-    betas.push_back(ch.sample_ext());
-  }
-  for (auto& c : P.final_poly) ch.observe_ext(c);
-  for (int la : las) ch.observe(F::from_canonical((uint32_t)la));
-  if (!ch.check_witness(prm.query_pow_bits, P.query_pow)) vfail("FRI: invalid query proof of work");
-  if ((int)P.queries.size() != prm.num_queries) vfail("FRI: %zu queries, expected %d", P.queries.size(), prm.num_queries);
 
-  // ---- queries
-  size_t max_w = 1;
-  for (auto& r : rounds) for (auto& m : r) max_w = std::max(max_w, (size_t)m.w);
-  std::vector<E> fa_pow(max_w + 1);
-  fa_pow[0] = E::one();
-  for (size_t c = 1; c <= max_w; ++c) fa_pow[c] = fa_pow[c - 1] * fri_alpha;
-  for (size_t qi = 0; qi < P.queries.size(); ++qi) {
+  void queries() {
+    for (size_t qi = 0; qi < P.queries.size(); ++qi) {
+      const size_t index = ch.sample_bits(log_max);
+      fold_chain(qi, index, input_openings(qi, index));
+    }
+  }
+
+  // the input batches of one query against their commitments, and its reduced openings per height: log_h -> (next
+  // alpha power, value), alpha powers restart per height (pcs/fri/verifier.rs:1068-1356)
+  using Reduced = std::map<int, std::pair<E, E>>;
+  Reduced input_openings(size_t qi, size_t index) const {
     const auto& Q = P.queries[qi];
-    const size_t index = ch.sample_bits(log_max);
+    const F gen = F::generator();
     if (Q.rounds.size() != rounds.size()) vfail("query %zu: %zu input batches, expected %zu", qi, Q.rounds.size(), rounds.size());
-    // reduced openings per height, alpha powers restart per height (pcs/fri/verifier.rs:1068-1356)
-    std::map<int, std::pair<E, E>> ro;  // log_h -> (next alpha power, value)
+    Reduced ro;
     for (size_t r = 0; r < rounds.size(); ++r) {
       std::vector<int> lhs;
       for (auto& m : rounds[r]) lhs.push_back(m.log_h);
@@ -1061,9 +731,7 @@ void verify_batch(const VerifyParams& prm, const std::vector<uint32_t>& rc_canon
       if (qr.rows.size() != rounds[r].size()) vfail("query %zu: batch %zu opens %zu matrices, expected %zu", qi, r, qr.rows.size(), rounds[r].size());
       for (size_t m = 0; m < rounds[r].size(); ++m)
         if (qr.rows[m].size() != (size_t)rounds[r][m].w) vfail("query %zu: batch %zu matrix %zu has the wrong width", qi, r, m);
-      const auto leaf_rows = salted_rows<F>(qr.rows, qr.salts, prm.mmcs_salt_elems, "input batch");
-      if (prm.mmcs_arity == 4) mmcs_verify4<PP>(*round_caps[r], cap_h, lhs, leaf_rows, index >> (log_max - r_max), qr.path, rc.data() + p2_num_constants<PP>(), "input batch");
-      else mmcs_verify<PP>(*round_caps[r], cap_h, lhs, leaf_rows, index >> (log_max - r_max), qr.path, rc.data(), "input batch");
+      mmcs.check_opening(*round_caps[r], cap_h, lhs, qr.rows, qr.salts, index >> (log_max - r_max), qr.path, "input batch");
       for (size_t m = 0; m < rounds[r].size(); ++m) {
         const Mat& M = rounds[r][m];
         auto it = ro.find(M.log_h);
@@ -1080,10 +748,15 @@ void verify_batch(const VerifyParams& prm, const std::vector<uint32_t>& rc_canon
         }
       }
     }
-    // fold chain (pcs/fri/verifier.rs:562-781)
+    return ro;
+  }
+
+  // the fold chain of one query down to the final polynomial (pcs/fri/verifier.rs:562-781)
+  void fold_chain(size_t qi, size_t index, const Reduced& ro) const {
+    const auto& Q = P.queries[qi];
     if (Q.phases.size() != las.size()) vfail("query %zu: %zu commit-phase openings, expected %zu", qi, Q.phases.size(), las.size());
     if (!ro.count(log_max)) vfail("query %zu: no reduced opening at the maximum height", qi);
-    E folded = ro[log_max].second;
+    E folded = ro.at(log_max).second;
     size_t idx = index;
     int cur = log_max;
     const F neg_half = -(F::from_canonical(2).inv());
@@ -1097,9 +770,7 @@ void verify_batch(const VerifyParams& prm, const std::vector<uint32_t>& rc_canon
       // the leaf is the row of 2^la sibling evaluations, extension elements flattened
       std::vector<F> leaf;
       for (auto& x : e) for (int k = 0; k < DC; ++k) leaf.push_back(x.c[k]);
-      const auto leaf_rows = salted_rows<F>({leaf}, ph.salts, prm.mmcs_salt_elems, "FRI commit phase");
-      if (prm.mmcs_arity == 4) mmcs_verify4<PP>(P.commit_caps[p], cap_h, {cur - la}, leaf_rows, row, ph.path, rc.data() + p2_num_constants<PP>(), "FRI commit phase");
-      else mmcs_verify<PP>(P.commit_caps[p], cap_h, {cur - la}, leaf_rows, row, ph.path, rc.data(), "FRI commit phase");
+      mmcs.check_opening(P.commit_caps[p], cap_h, {cur - la}, {leaf}, ph.salts, row, ph.path, "FRI commit phase");
       F ss_inv = F::two_adic_generator(cur).inv().pow(bit_reverse((uint32_t)row, cur - la));
       E b = betas[p];
       const F omega = F::two_adic_generator(la);
@@ -1127,6 +798,21 @@ void verify_batch(const VerifyParams& prm, const std::vector<uint32_t>& rc_canon
     for (size_t k = P.final_poly.size(); k-- > 0;) eval = eval * x + P.final_poly[k];
     if (!(eval == folded)) vfail("query %zu: final polynomial mismatch", qi);
   }
+};
+
+template <class PP, int DC = 4>
+void verify_batch(const VerifyParams& prm, const std::vector<uint32_t>& rc_canonical, const std::vector<AirParams>& airs,
+                  const std::vector<uint32_t>& prep_cap_canonical, const std::vector<uint32_t>& expected_degree_bits,
+                  const uint8_t* bytes, size_t n_bytes, bool canonical) {
+  if (prm.zk && (prm.num_random_codewords < 1 || prm.num_random_codewords > 8)) vfail("num_random_codewords must be in 1..8");
+  if (prm.mmcs_salt_elems < 0 || prm.mmcs_salt_elems > 16) vfail("mmcs_salt_elems must be in 0..16");
+  BatchVerifier<PP, DC> V(prm, rc_canonical, airs, prep_cap_canonical, bytes, n_bytes, canonical);
+  V.shapes(expected_degree_bits);
+  V.transcript_head();
+  V.opening_rounds();
+  V.constraints_at_zeta();
+  V.fri_commit_phase();
+  V.queries();
 }
 
 }  // namespace p3r

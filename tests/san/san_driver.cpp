@@ -1,7 +1,8 @@
 // Driver of the sanitizer build (tests/san/Makefile): a structure-aware mutator over REAL proofs and circuits, run
 // in-process against the ASan + UBSan build of the library's host-only code (san_host.hip).  Test infrastructure.
 //
-//   san_driver proofs  <case file> <iterations> <seed>     proof bytes  -> p3r_batch_stark_proof_parse, p3r_batch_proof_len_layout,
+//   san_driver proofs  <case file> <iterations> <seed>     proof bytes  -> p3r_batch_stark_proof_parse, p3r_batch_proof_len_layout
+//                                                           (held against the building sink alone, san_proof_build),
 //                                                           p3r::BatchStarkProof::from_postcard / to_postcard (include/p3r.hpp),
 //                                                           p3r_verify_batch (when the bytes still parse)
 //   san_driver mmcs    <case file> <iterations> <seed>     p3r_mmcs_verify on the openings inside the case's proof, with mutated
@@ -14,7 +15,10 @@
 // validation rules are about (batch_stark_prover.rs:459-488,666-681, packing.rs:140-161), besides unstructured byte flips.
 // A mutant must be REFUSED or - if it is still the same proof with different metadata - verify; it must never be accepted
 // with different inner bytes, and nothing may trip a sanitizer (the process aborts: -fno-sanitize-recover).
-// Exit code 0 and one summary line on success.
+// Exit code 0 and one summary line on success.  `outcome_hash` in it: 64-bit FNV-1a over every outcome (entry point,
+// return code, error text of a refusal, returned length) of p3r_batch_proof_len_layout, p3r_batch_stark_proof_parse,
+// p3r_verify_batch and p3r_mmcs_verify, in call order - case file, iteration count and seed fix it, so two builds of the
+// library that differ in any code, text or length on any mutant print different values.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +29,7 @@
 #include "../../include/p3r.hpp"
 
 extern "C" int san_circuit_host_prep(const p3r_circuit_desc* d, uint32_t field, uint32_t ext_degree, char* err, size_t err_cap);
+extern "C" int san_proof_build(uint32_t field, const uint8_t* bytes, size_t len, uint32_t flags, size_t* consumed, char* err, size_t err_cap);
 
 namespace {
 
@@ -57,6 +62,22 @@ struct In {
     T v; memcpy(&v, p, sizeof(T)); p += sizeof(T); return v;
   }
   std::vector<uint32_t> words(size_t n) { std::vector<uint32_t> v(n); for (auto& x : v) x = get<uint32_t>(); return v; }
+};
+
+enum Entry : uint8_t { E_PROOF_LEN = 1, E_PARSE, E_VERIFY, E_MMCS };
+struct Outcomes {
+  uint64_t h = 0xCBF29CE484222325ull;
+  void bytes(const void* p, size_t n) {
+    for (size_t i = 0; i < n; ++i) h = (h ^ ((const uint8_t*)p)[i]) * 0x100000001B3ull;
+  }
+  // `err` counts for a refusal only (a call that succeeds leaves the buffer alone), `len` for a success only
+  int fold(Entry e, int rc, const char* err, uint64_t len = 0) {
+    const int32_t code = rc;
+    if (rc != P3R_OK) len = 0;
+    bytes(&e, 1); bytes(&code, sizeof code); bytes(&len, sizeof len);
+    if (rc != P3R_OK) bytes(err, strlen(err) + 1);
+    return rc;
+  }
 };
 
 void put_varint(std::vector<uint8_t>& o, uint64_t v) {
@@ -357,6 +378,7 @@ int run_proofs(const char* path, uint64_t iters, uint64_t seed) {
   Case c = load_case(path);
   char err[512];
   p3r_batch_stark_meta meta;
+  Outcomes out;
   if (p3r_batch_stark_proof_parse(c.cfg.field, c.outer.data(), c.outer.size(), c.flags, nullptr, &meta, err, sizeof err) != P3R_OK) {
     fprintf(stderr, "the seed proof does not parse: %s\n", err);
     return 1;
@@ -382,8 +404,23 @@ int run_proofs(const char* path, uint64_t iters, uint64_t seed) {
     uint8_t* buf = (uint8_t*)malloc(m.size() ? m.size() : 1);
     if (!m.empty()) memcpy(buf, m.data(), m.size());   // (an empty mutant has a null data(): memcpy's arguments must not be - UBSan, at 10 x the default volume)
     size_t plen = 0;
-    (void)p3r_batch_proof_len_layout(c.cfg.field, buf, m.size(), c.flags, nullptr, &plen, err, sizeof err);
+    err[0] = 0;
+    const int lrc = p3r_batch_proof_len_layout(c.cfg.field, buf, m.size(), c.flags, nullptr, &plen, err, sizeof err);
+    out.fold(E_PROOF_LEN, lrc, err, plen);
+    // the two sinks of the one grammar (csrc/proof_grammar.h) agree on every mutant: code, text, consumed length
+    {
+      char berr[512] = "";
+      size_t blen = 0;
+      const int brc = san_proof_build(c.cfg.field, buf, m.size(), c.flags, &blen, berr, sizeof berr);
+      if (brc != lrc || (lrc == P3R_OK ? blen != plen : strcmp(berr, err) != 0)) {
+        fprintf(stderr, "iteration %llu (seed %llu): the building sink returns (%d, \"%s\", %zu), the checking sink (%d, \"%s\", %zu)\n",
+                (unsigned long long)it, (unsigned long long)seed, brc, berr, blen, lrc, err, plen);
+        return 1;
+      }
+    }
+    err[0] = 0;
     const int rc = p3r_batch_stark_proof_parse(c.cfg.field, buf, m.size(), c.flags, nullptr, &meta, err, sizeof err);
+    out.fold(E_PARSE, rc, err, rc == P3R_OK ? meta.proof_len : 0);
     if (rc != P3R_OK) { ++rejected_parse; free(buf); continue; }
     ++parsed;
     // the C++ mirror (include/p3r.hpp): parse -> object -> bytes must reproduce what was parsed
@@ -395,7 +432,8 @@ int run_proofs(const char* path, uint64_t iters, uint64_t seed) {
     const bool same_inner = meta.proof_len == inner.size() && memcmp(buf, inner.data(), inner.size()) == 0;
     uint8_t* ib = (uint8_t*)malloc(meta.proof_len ? meta.proof_len : 1);
     memcpy(ib, buf, meta.proof_len);
-    const int vrc = p3r_verify_batch(&c.cfg, c.airs.data(), c.airs.size(), c.cap.data(), c.degree_bits.data(), ib, meta.proof_len, 0, err, sizeof err);
+    err[0] = 0;
+    const int vrc = out.fold(E_VERIFY, p3r_verify_batch(&c.cfg, c.airs.data(), c.airs.size(), c.cap.data(), c.degree_bits.data(), ib, meta.proof_len, 0, err, sizeof err), err);
     free(ib);
     free(buf);
     if (vrc == P3R_OK) {
@@ -415,9 +453,10 @@ int run_proofs(const char* path, uint64_t iters, uint64_t seed) {
     }
   }
   printf("{\"mode\": \"proofs\", \"iterations\": %llu, \"rejected_by_parser\": %llu, \"parsed\": %llu, \"rejected_by_verifier\": %llu, "
-         "\"same_proof_other_metadata_verified\": %llu, \"zero_bit_pow_witness_changed_verified\": %llu, \"hpp_round_trips\": %llu}\n",
+         "\"same_proof_other_metadata_verified\": %llu, \"zero_bit_pow_witness_changed_verified\": %llu, \"hpp_round_trips\": %llu, "
+         "\"outcome_hash\": %llu}\n",
          (unsigned long long)iters, (unsigned long long)rejected_parse, (unsigned long long)parsed, (unsigned long long)rejected_verify,
-         (unsigned long long)verified_same, (unsigned long long)unbound_pow, (unsigned long long)hpp_ok);
+         (unsigned long long)verified_same, (unsigned long long)unbound_pow, (unsigned long long)hpp_ok, (unsigned long long)out.h);
   return 0;
 }
 
@@ -427,6 +466,7 @@ int run_mmcs(const char* path, uint64_t iters, uint64_t seed) {
   Rng r{seed};
   char err[512];
   uint64_t ok = 0, bad = 0;
+  Outcomes out;
   const uint32_t P = c.cfg.field == P3R_FIELD_KOALA_BEAR ? 0x7F000001u : 0x78000001u;
   for (uint64_t it = 0; it < iters; ++it) {
     p3r_config cfg = c.cfg;
@@ -453,11 +493,13 @@ int run_mmcs(const char* path, uint64_t iters, uint64_t seed) {
     for (auto& x : cap) x = r.below(9) ? (uint32_t)r.below(P) : (uint32_t)r.next();
     for (auto& x : opened) x = r.below(30) ? (uint32_t)r.below(P) : (uint32_t)r.next();
     for (auto& x : proof) x = (uint32_t)r.below(P);
-    const int rc = p3r_mmcs_verify(&cfg, cap.data(), n_mats, hs.data(), ws.data(), (size_t)r.next() >> r.below(64), opened.data(),
-                                   proof.data(), proof_len, err, sizeof err);
+    err[0] = 0;
+    const int rc = out.fold(E_MMCS, p3r_mmcs_verify(&cfg, cap.data(), n_mats, hs.data(), ws.data(), (size_t)r.next() >> r.below(64), opened.data(),
+                                                    proof.data(), proof_len, err, sizeof err), err);
     (rc == P3R_OK ? ok : bad)++;
   }
-  printf("{\"mode\": \"mmcs\", \"iterations\": %llu, \"accepted\": %llu, \"refused\": %llu}\n", (unsigned long long)iters, (unsigned long long)ok, (unsigned long long)bad);
+  printf("{\"mode\": \"mmcs\", \"iterations\": %llu, \"accepted\": %llu, \"refused\": %llu, \"outcome_hash\": %llu}\n", (unsigned long long)iters,
+         (unsigned long long)ok, (unsigned long long)bad, (unsigned long long)out.h);
   return ok ? 1 : 0;   // random digests never open a random cap
 }
 

@@ -41,4 +41,26 @@ int san_circuit_host_prep(const p3r_circuit_desc* d, uint32_t field, uint32_t ex
   }
 }
 
+// The building sink of csrc/proof_grammar.h alone over the BatchProof at the head of `bytes` (what verify_batch parses
+// with): code, text and the consumed length.  The driver holds it against p3r_batch_proof_len_layout, the checking sink
+// over the same walk, on every mutant.
+int san_proof_build(uint32_t field, const uint8_t* bytes, size_t len, uint32_t flags, size_t* consumed, char* err, size_t err_cap) {
+  return guarded(err, err_cap, [&] {
+    if (!bytes || !consumed) refuse(P3R_EINVAL, "NULL argument");
+    const ProofFlags f(flags, nullptr);
+    for_field(field, [&](auto tag) {
+      using PP = decltype(tag);
+      auto build = [&](auto dc) {
+        ProofBuilder<PP, decltype(dc)::value> B(bytes, len, f.canonical);
+        *consumed = walk_batch_proof(B, f.PL, f.zk, f.salted, true);
+      };
+      if constexpr (kHasQuintic<PP>) {
+        if (f.quintic) return build(std::integral_constant<int, 5>{});
+      }
+      build(std::integral_constant<int, 4>{});
+    });
+    return P3R_OK;
+  });
+}
+
 }  // extern "C"
