@@ -678,6 +678,78 @@ int p3r_logup_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insn
                            const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
                            p3r_dmat** out, uint32_t* sum_out /* DC, HOST */);
 
+/* ---- is the trace right?  Unsatisfied constraints and unbalanced lookups of resident traces, located ----
+ *
+ * Functions are only added: P3R_ABI_VERSION stays as it is, no op is added, and no entry above changes.
+ *
+ * A broken constraint otherwise shows up at the far end, as p3r_fri_final_poly_dmat refusing with "the input is not of
+ * low degree"; an unbalanced bus as table sums that do not cancel.  Neither names a row, a constraint or a tuple.  The
+ * reference has both tools and uses them on this path: DebugConstraintBuilder runs Air::eval on every (row, next row)
+ * pair with 0/1 selectors and reports the first failing row (test-utils/src/lib.rs:165-260, check_air_satisfies; every
+ * table wrapper of the batch prover implements it: batch_stark_prover.rs:883-890, poseidon2.rs:808-822,
+ * dynamic_air.rs:138-248), and p3_lookup::debug_util::check_lookups runs over all instances before prove_batch when
+ * debug_lookups is set (batch_stark_prover.rs:1546-1593).  Both entries refuse zk contexts (P3R_EUNSUPPORTED), as the
+ * two program seams do, and both WAIT for the stream.
+ *
+ * p3r_check_program_dmat: a constraint program (the p3r_air_insn form of p3r_quotient_program_dmat) on the TRACE domain.
+ * The inputs are traces, not LDEs: h rows, h a power of two, in natural order, all matrices of one height - the lookup
+ * seam's convention.  Row r is the current row and (r + 1) mod h the next one (h = 1: the row itself).  The selectors
+ * take the values of DebugConstraintBuilder: is_first_row = [r == 0], is_last_row = [r == h - 1], is_transition =
+ * [r != h - 1].  Constraint k is the k-th ASSERT_ZERO; it fails in row r when its value is non-zero - for an extension
+ * value, when any coefficient is.  first_row_out[k] (HOST, n_constraints words, may be NULL) is the smallest failing row of
+ * constraint k, or 0xffffffff if there is none; n_failed_out[k] (HOST, may be NULL) its number of failing rows.  The report
+ * is derived from those two arrays on the host.  A trace that does not satisfy the program is a RESULT, not an error:
+ * the call returns P3R_OK.
+ * Refusals, with a message, before anything is allocated or launched: what p3r_quotient_program_dmat refuses about
+ * programs, operands, matrices, indices and non-canonical words (LOOKUP and LOOKUP_END stay unknown ops here), what
+ * p3r_logup_program_dmat refuses about heights, a NULL report (P3R_EINVAL); more live values than P3R_AIR_MAX_LIVE, zk
+ * contexts (P3R_EUNSUPPORTED).  The interpreter is the one of the two seams above with a third sink: one wave-wide vote
+ * per constraint, and at most two atomic operations per wave and constraint - none at all on a satisfying trace.
+ *
+ * p3r_lookup_check_dmat: the multiset balance of lookup programs across tables.  An instance is a lookup program as
+ * p3r_logup_program_dmat takes it, with its traces (one height per instance) and public values; the challenges are
+ * shared.  Every LOOKUP term t of instance p in row r with a non-zero multiplicity is a record (d, m), both lifted to
+ * the challenge field; a term with zero multiplicity is no record.  Record order is lexicographic in (instance, row,
+ * term).  The key of a record is its denominator value: with the caller's challenges, equal tuples on one bus are equal
+ * denominators; the grouping into columns (LOOKUP_END) does not matter here.  Nothing is inverted - a zero denominator is
+ * an ordinary key.  A key is unbalanced when the sum of its multiplicities is non-zero.  *n_unbalanced_out counts the
+ * unbalanced keys; `out` receives the min(cap, count) of them whose first records come earliest in record order,
+ * ascending: the place of the key's first record, the number of records that share the key, the key (canonical, DC words
+ * used, the rest zero) and the sum of its multiplicities (canonical, non-zero).  The call returns P3R_OK whatever the
+ * count.
+ * Refusals, before anything is allocated or launched: each instance for what p3r_logup_program_dmat would refuse it for
+ * (the message names the instance); n_inst == 0, a NULL n_unbalanced_out, a NULL out with cap > 0 (P3R_EINVAL); more
+ * than P3R_LOOKUP_CHECK_MAX_RECORDS term slots sum_p h_p * n_terms_p, zk contexts (P3R_EUNSUPPORTED).
+ * The records are written by the interpreter with a fourth sink, compacted, ordered by key with a stable radix sort
+ * (least significant coefficient word first), and summed per run of equal keys with exclusive sums of 64-bit words; the
+ * device memory it takes, about (2 DC + 1) words per slot and 4 DC + 10 per record, is freed before it returns. */
+typedef struct p3r_check_report {
+  uint64_t n_failures;        /* (row, constraint) pairs whose asserted value is not zero */
+  uint32_t first_row;         /* smallest failing row; 0xffffffff: the trace satisfies the program */
+  uint32_t first_constraint;  /* smallest failing constraint in that row */
+} p3r_check_report;
+int p3r_check_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,
+                           const uint32_t* public_values, size_t n_public,
+                           const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
+                           p3r_check_report* report, uint32_t* first_row_out /* n_constraints, may be NULL */,
+                           uint64_t* n_failed_out /* n_constraints, may be NULL */);
+#define P3R_LOOKUP_CHECK_MAX_RECORDS (1u << 28)
+typedef const p3r_dmat* p3r_dmat_cptr;           /* so that a member below reads as one pointer to one word: the type is the same */
+typedef struct p3r_lookup_instance {
+  const p3r_air_insn* prog; size_t n_insns;      /* a lookup program, as p3r_logup_program_dmat takes it */
+  const p3r_dmat_cptr* mats; size_t n_mats;      /* = const p3r_dmat* const* mats: its traces, one height per instance */
+  const uint32_t* public_values; size_t n_public;
+} p3r_lookup_instance;
+typedef struct p3r_lookup_imbalance {
+  uint32_t instance, row, term;   /* the first record of the key, in record order */
+  uint32_t n_records;             /* records that share the key */
+  uint32_t denominator[5];        /* the key, canonical, DC words used */
+  uint32_t net[5];                /* the sum of its multiplicities, canonical, non-zero */
+} p3r_lookup_imbalance;
+int p3r_lookup_check_dmat(p3r_ctx* ctx, const p3r_lookup_instance* inst, size_t n_inst,
+                          const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
+                          p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out);
+
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *
  * p3r_prep_create  == ProverData::from_airs_and_degrees + CircuitProverData::new as called by

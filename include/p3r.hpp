@@ -17,6 +17,7 @@
 //   ProveNextLayerParams, RecursionInput, RecursionOutput, NextLayerPrepCache,
 //   build_next_layer_prep, prove_next_layer                   recursion/src/recursion.rs:96-139,221-234,295-298,342-502
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -342,6 +343,56 @@ inline LogupTrace logup_trace(const Context& ctx, const AirProgram& program, con
   ctx.check(p3r_logup_program_dmat(ctx.raw(), program.insns().data(), program.insns().size(), mats.data(), mats.size(),
                                    public_values.data(), public_values.size(), challenges.data(), challenges.size() / dc, &out.trace,
                                    out.sum.data()));
+  return out;
+}
+
+// check_air_satisfies over device matrices (p3r.h: p3r_check_program_dmat): the constraint `program` on every row of the
+// TRACES `mats` (one height, natural order, not LDEs) with DebugConstraintBuilder's 0 / 1 selectors.  report.first_row is
+// 0xffffffff when the trace satisfies the program; first_row[k] / n_failed[k] are the smallest failing row (0xffffffff:
+// none) and the number of failing rows of constraint k.  A failing trace is a result, not an Error.  Waits for the device.
+struct ConstraintCheck {
+  p3r_check_report report;
+  std::vector<uint32_t> first_row;
+  std::vector<uint64_t> n_failed;
+  bool satisfied() const { return report.first_row == 0xffffffffu; }
+};
+inline ConstraintCheck check_constraints(const Context& ctx, const AirProgram& program, const std::vector<const p3r_dmat*>& mats,
+                                         const std::vector<uint32_t>& public_values = {}, const std::vector<uint32_t>& challenges = {}) {
+  const size_t dc = ctx.config().challenge_degree ? ctx.config().challenge_degree : 4;
+  if (challenges.size() % dc) throw Error(P3R_EINVAL, "challenges are DC words each");
+  size_t n_constraints = 0;
+  for (const p3r_air_insn& in : program.insns()) n_constraints += in.op == P3R_AIR_ASSERT_ZERO;
+  ConstraintCheck out{{}, std::vector<uint32_t>(n_constraints, 0xffffffffu), std::vector<uint64_t>(n_constraints, 0)};
+  ctx.check(p3r_check_program_dmat(ctx.raw(), program.insns().data(), program.insns().size(), mats.data(), mats.size(),
+                                   public_values.data(), public_values.size(), challenges.data(), challenges.size() / dc, &out.report,
+                                   out.first_row.data(), out.n_failed.data()));
+  return out;
+}
+
+// p3_lookup::debug_util::check_lookups over device matrices (p3r.h: p3r_lookup_check_dmat): the tables of a bus, each a
+// lookup program with its traces and public values; the challenges are shared.  `unbalanced` holds at most `cap` of the
+// `n_unbalanced` keys whose multiplicities do not cancel, those whose first records come earliest.  Waits for the device.
+struct LookupTable {
+  const AirProgram* program;
+  std::vector<const p3r_dmat*> mats;
+  std::vector<uint32_t> public_values;
+};
+struct LookupCheck {
+  uint64_t n_unbalanced;
+  std::vector<p3r_lookup_imbalance> unbalanced;
+};
+inline LookupCheck check_lookups(const Context& ctx, const std::vector<LookupTable>& tables, const std::vector<uint32_t>& challenges = {},
+                                 size_t cap = 16) {
+  const size_t dc = ctx.config().challenge_degree ? ctx.config().challenge_degree : 4;
+  if (challenges.size() % dc) throw Error(P3R_EINVAL, "challenges are DC words each");
+  std::vector<p3r_lookup_instance> inst;
+  for (const LookupTable& t : tables)
+    inst.push_back(p3r_lookup_instance{t.program->insns().data(), t.program->insns().size(), t.mats.data(), t.mats.size(),
+                                       t.public_values.data(), t.public_values.size()});
+  LookupCheck out{0, std::vector<p3r_lookup_imbalance>(cap)};
+  ctx.check(p3r_lookup_check_dmat(ctx.raw(), inst.data(), inst.size(), challenges.data(), challenges.size() / dc, out.unbalanced.data(), cap,
+                                  &out.n_unbalanced));
+  out.unbalanced.resize((size_t)std::min<uint64_t>(cap, out.n_unbalanced));
   return out;
 }
 

@@ -23,6 +23,7 @@ P3R_EXT_ZK_DETERMINISTIC = 4        # ZK key taken as it is, p3r_zk_set_nonce al
 # the sinks of a lookup program (p3r_logup_program_dmat); unknown ops to the constraint-program entries
 P3R_AIR_LOOKUP, P3R_AIR_LOOKUP_END = 21, 22
 P3R_AIR_MAX_LIVE = 48
+P3R_LOOKUP_CHECK_MAX_RECORDS = 1 << 28    # p3r_lookup_check_dmat: term slots (rows x terms over the instances) of one call
 FIELD_KOALA_BEAR = 0
 FIELD_BABY_BEAR = 1
 
@@ -96,6 +97,20 @@ class P3rAirInfo(C.Structure):
 class P3rLookupInfo(C.Structure):
     _fields_ = [("n_terms", C.c_uint32), ("n_columns", C.c_uint32), ("max_terms_per_column", C.c_uint32),
                 ("max_constraint_degree", C.c_uint32), ("peak_live", C.c_uint32)]
+
+
+class P3rCheckReport(C.Structure):   # p3r_check_program_dmat
+    _fields_ = [("n_failures", C.c_uint64), ("first_row", C.c_uint32), ("first_constraint", C.c_uint32)]
+
+
+class P3rLookupInstance(C.Structure):   # p3r_lookup_check_dmat: one table on the bus
+    _fields_ = [("prog", C.POINTER(P3rAirInsn)), ("n_insns", C.c_size_t), ("mats", C.POINTER(C.c_void_p)), ("n_mats", C.c_size_t),
+                ("public_values", C.POINTER(C.c_uint32)), ("n_public", C.c_size_t)]
+
+
+class P3rLookupImbalance(C.Structure):   # p3r_lookup_check_dmat: one unbalanced key
+    _fields_ = [("instance", C.c_uint32), ("row", C.c_uint32), ("term", C.c_uint32), ("n_records", C.c_uint32),
+                ("denominator", C.c_uint32 * 5), ("net", C.c_uint32 * 5)]
 
 
 class P3rAirDesc(C.Structure):
@@ -251,6 +266,11 @@ SIGNATURES = {
                                           C.POINTER(P3rLookupInfo)]),
     "p3r_logup_program_dmat": (C.c_int, [vp, C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(vp), C.c_size_t, u32p, C.c_size_t, u32p,
                                          C.c_size_t, C.POINTER(vp), u32p]),
+    # is the caller's trace right: unsatisfied constraints and unbalanced lookups of resident traces
+    "p3r_check_program_dmat": (C.c_int, [vp, C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(vp), C.c_size_t, u32p, C.c_size_t, u32p,
+                                         C.c_size_t, C.POINTER(P3rCheckReport), u32p, C.POINTER(C.c_uint64)]),
+    "p3r_lookup_check_dmat": (C.c_int, [vp, C.POINTER(P3rLookupInstance), C.c_size_t, u32p, C.c_size_t, C.POINTER(P3rLookupImbalance),
+                                        C.c_size_t, C.POINTER(C.c_uint64)]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

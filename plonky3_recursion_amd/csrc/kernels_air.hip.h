@@ -7,9 +7,13 @@
 //   k_logup_program      p3r_logup_program_dmat: the caller's lookups on every row of resident TRACES - the fraction columns
 //                        of the permutation trace and each row's total; the running sum is k_ef_scan's (kernels_stark.hip.h).
 //                        The prover's own k_logup_aux keeps the interactions of the built-in tables inlined.
+//   k_check_program      p3r_check_program_dmat: the caller's constraints on every row of resident TRACES with 0 / 1
+//                        selectors - per constraint the smallest row in which it does not vanish and the number of such rows.
+//   k_lookup_records     p3r_lookup_check_dmat: the caller's lookups on every row of resident TRACES - every term's
+//                        denominator and multiplicity as canonical words, for the sort and the sums of tu_air.hip.
 //
-// Both are one interpreter, air_step, with the sinks as a template parameter (QuotProgSink / LogupProgSink), as AuxSink /
-// QuotSink share air_interactions for the built-in AIRs.
+// All four are one interpreter, air_step, with the sinks as a template parameter (QuotProgSink / LogupProgSink /
+// CheckProgSink / RecordSink), as AuxSink / QuotSink share air_interactions for the built-in AIRs.
 //
 // One lane per row: of the quotient domain in storage (bit-reversed) order, of a trace in natural order - either way the
 // read of a column at the current row is one contiguous run per wave; the next row's read is the same run bit-reversal
@@ -250,6 +254,144 @@ __global__ void __launch_bounds__(kAirLanes) k_logup_program(AirLogupArgs a) {
   const gptr<uint32_t> rowsum = as_global(a.rowsum);
 #pragma unroll
   for (int k = 0; k < DC; ++k) rowsum[(size_t)k * h + r] = sink.total.c[k].v;
+}
+
+// The sinks of a constraint program on the trace domain (DebugConstraintBuilder): the selectors are 0 / 1 by the lane's
+// row, and an asserted value is looked at, not folded.  Every lane of the wave stands at the same ASSERT (the instruction
+// stream is wave-uniform), so one ballot of "not zero" over the wave's active lanes says whether any row failed; only then
+// does ONE lane - the lowest failing one - add the popcount to the constraint's counter and offer the wave's smallest
+// failing row to its first_row.  At most two atomics per wave and constraint, none at all on a satisfying trace.
+// The constraint's ordinal is counted here: one ASSERT, one increment, the same in every lane.
+template <class PP, int DC>
+struct CheckProgSink {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  F is_first, is_last, is_transition;
+  uint32_t* first_row;
+  unsigned long long* n_failed;
+  uint32_t wave_row;   // the row of the wave's lane 0
+  uint32_t k;          // constraints met so far
+  __device__ __forceinline__ void vote(bool bad) {
+    const uint64_t failing = __ballot(bad);
+    if (failing) {
+      const uint32_t low = (uint32_t)__ffsll((unsigned long long)failing) - 1u;
+      if (threadIdx.x == low) {
+        atomicAdd(n_failed + k, (unsigned long long)__popcll(failing));
+        atomicMin(first_row + k, wave_row + low);
+      }
+    }
+    ++k;
+  }
+  __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
+    switch (in.op) {
+      case AIR_D_FIRST: sl.st(in.dst, is_first); break;
+      case AIR_D_LAST: sl.st(in.dst, is_last); break;
+      case AIR_D_TRANS: sl.st(in.dst, is_transition); break;
+      case AIR_D_ASSERT_B: vote(sl.ld(in.a).v != 0); break;
+      case AIR_D_ASSERT_E: vote(!sl.lde(in.a).is_zero()); break;
+      default: break;   // air_compile emits nothing else for a constraint program
+    }
+  }
+};
+
+struct AirCheckArgs {
+  const AirDevInsn* insns;         // n_insns of them
+  const uint32_t* ext_consts;      // Montgomery, DC words per entry
+  const uint32_t* const* cols;     // one pointer per flat column: h words, natural order
+  uint32_t* first_row;             // [n_constraints], 0xffffffff before the launch
+  unsigned long long* n_failed;    // [n_constraints], 0 before the launch
+  uint32_t n_insns;
+  int log_h;
+};
+
+template <class PP, int DC>
+__global__ void __launch_bounds__(kAirLanes) k_check_program(AirCheckArgs a) {
+  using F = Fp<PP>;
+  extern __shared__ uint32_t air_slots[];
+  const size_t h = size_t(1) << a.log_h;
+  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
+  if (r >= h) return;   // h < 64: the ballots see the active lanes only
+  const size_t r_next = (r + 1) & (h - 1);
+  CheckProgSink<PP, DC> sink;
+  sink.is_first = r == 0 ? F::one() : F::zero();
+  sink.is_last = r == h - 1 ? F::one() : F::zero();
+  sink.is_transition = r == h - 1 ? F::zero() : F::one();
+  sink.first_row = a.first_row;
+  sink.n_failed = a.n_failed;
+  sink.wave_row = blockIdx.x * (uint32_t)kAirLanes;
+  sink.k = 0;
+
+  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
+  const gptr<const AirDevInsn> insns = as_global(a.insns);
+  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
+  const gptr<const uint32_t* const> cols = as_global(a.cols);
+  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
+}
+
+// The sinks of a lookup program whose terms are recorded, not summed: term t of row r is slot base + r * n_terms + t of
+// the call - the slots of a call are its records in record order (instance, row, term) - and writes the canonical words
+// of its denominator and multiplicity, both lifted, to [word][slot], and whether the multiplicity is not zero to
+// mark[slot].  Nothing is inverted and a column end does nothing.  The lanes of a wave write n_terms words apart; the
+// n_terms writes of a row fill the lines between.  The term's ordinal is counted here, as CheckProgSink counts constraints.
+template <class PP, int DC>
+struct RecordSink {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  gptr<uint32_t> den, mul, mark;
+  size_t n_slots, slot;   // slot: of the row's next term
+  __device__ __forceinline__ void put(const E& m, const E& d) {
+#pragma unroll
+    for (int k = 0; k < DC; ++k) {
+      den[(size_t)k * n_slots + slot] = d.c[k].to_canonical();
+      mul[(size_t)k * n_slots + slot] = m.c[k].to_canonical();
+    }
+    mark[slot] = m.is_zero() ? 0u : 1u;
+    ++slot;
+  }
+  __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
+    switch (in.op) {
+      case AIR_D_TERM_BB: put(E::from_base(sl.ld(in.a)), E::from_base(sl.ld(in.b))); break;
+      case AIR_D_TERM_BE: put(E::from_base(sl.ld(in.a)), sl.lde(in.b)); break;
+      case AIR_D_TERM_EB: put(sl.lde(in.a), E::from_base(sl.ld(in.b))); break;
+      case AIR_D_TERM_EE: put(sl.lde(in.a), sl.lde(in.b)); break;
+      default: break;   // COL_END: the grouping into columns does not matter to the balance
+    }
+  }
+};
+
+struct AirRecordArgs {
+  const AirDevInsn* insns;         // n_insns of them
+  const uint32_t* ext_consts;      // Montgomery, DC words per entry
+  const uint32_t* const* cols;     // one pointer per flat column: h words, natural order
+  uint32_t* den;                   // [DC][n_slots], canonical
+  uint32_t* mul;                   // [DC][n_slots], canonical
+  uint32_t* mark;                  // [n_slots]
+  size_t n_slots;                  // of the whole call
+  size_t base;                     // first slot of this instance
+  uint32_t n_terms;                // LOOKUPs of the program
+  uint32_t n_insns;
+  int log_h;
+};
+
+template <class PP, int DC>
+__global__ void __launch_bounds__(kAirLanes) k_lookup_records(AirRecordArgs a) {
+  extern __shared__ uint32_t air_slots[];
+  const size_t h = size_t(1) << a.log_h;
+  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
+  if (r >= h) return;
+  const size_t r_next = (r + 1) & (h - 1);
+  RecordSink<PP, DC> sink;
+  sink.den = as_global(a.den);
+  sink.mul = as_global(a.mul);
+  sink.mark = as_global(a.mark);
+  sink.n_slots = a.n_slots;
+  sink.slot = a.base + r * a.n_terms;
+
+  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
+  const gptr<const AirDevInsn> insns = as_global(a.insns);
+  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
+  const gptr<const uint32_t* const> cols = as_global(a.cols);
+  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
 }
 
 }  // namespace p3r

@@ -902,6 +902,40 @@ int p3r_logup_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insn
   });
 }
 
+// Is the caller's trace right: the constraints on the trace domain and the balance of the bus (tu_air.hip)
+int p3r_check_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,
+                           const uint32_t* public_values, size_t n_public, const uint32_t* challenges, size_t n_challenges,
+                           p3r_check_report* report, uint32_t* first_row_out, uint64_t* n_failed_out) {
+  return guard(ctx, [&] {
+    if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
+    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
+    std::vector<const p3r_dmat*> ms(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
+      ms[i] = mats[i];
+    }
+    P3R_FIELD_CALL(ctx, check_program, ctx, prog, n_insns, ms, public_values, n_public, challenges, n_challenges, report, first_row_out,
+                   n_failed_out);
+  });
+}
+int p3r_lookup_check_dmat(p3r_ctx* ctx, const p3r_lookup_instance* inst, size_t n_inst, const uint32_t* challenges, size_t n_challenges,
+                          p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out) {
+  return guard(ctx, [&] {
+    if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
+    if (n_inst && !inst) fail(P3R_EINVAL, "inst is NULL");
+    std::vector<LookupCheckInstance> is(n_inst);
+    for (size_t p = 0; p < n_inst; ++p) {
+      if (inst[p].n_mats && !inst[p].mats) fail(P3R_EINVAL, "instance %zu: mats is NULL", p);
+      is[p] = LookupCheckInstance{inst[p].prog, inst[p].n_insns, {}, inst[p].public_values, inst[p].n_public};
+      for (size_t i = 0; i < inst[p].n_mats; ++i) {
+        if (!inst[p].mats[i]) fail(P3R_EINVAL, "instance %zu: matrix %zu is NULL", p, i);
+        is[p].mats.push_back(inst[p].mats[i]);
+      }
+    }
+    P3R_FIELD_CALL(ctx, lookup_check, ctx, is, challenges, n_challenges, out, cap, n_unbalanced_out);
+  });
+}
+
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,
                          uint32_t* cap_out, p3r_tree** tree_out) {
   return guard(ctx, [&] {

@@ -4,6 +4,12 @@
 // k_quotient_program (kernels_air.hip.h).  One launch per call, whatever the program; the call only enqueues.
 // The lookup-program seam (p3r_logup_program_dmat) lives here too: the same host half in its lookup mode, the same
 // interpreter with the lookup sinks (k_logup_program), and the prover's scan for the running sum.
+// So do the two checks of a caller's traces: p3r_check_program_dmat (k_check_program: the constraints on the trace domain,
+// a first failing row and a count per constraint) and p3r_lookup_check_dmat (k_lookup_records, then the stable radix sort
+// and the sums of device_prims.hip.h: the keys of the bus whose multiplicities do not cancel).
+#include <algorithm>
+
+#include "device_prims.hip.h"
 #include "kernels_air.hip.h"
 #include "profile.h"
 #include "tu_api.h"
@@ -110,6 +116,66 @@ std::vector<std::unique_ptr<p3r_dmat>> quotient_program_dc(p3r_ctx* ctx, const p
   return outs;
 }
 
+// What the entries that run a program on TRACES (the lookup-program seam and the two checks) refuse about one program
+// and its matrices, in one order for all of them, and what they keep of it: the plan, and the figures of the launch.
+struct TraceProgram {
+  AirPlan plan;
+  std::vector<size_t> widths;
+  size_t h = 0, n_cols = 0, lds = 0;
+  int log_h = 0;
+};
+template <class PP, int DC>
+TraceProgram trace_program(const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats, const uint32_t* publics,
+                           size_t n_public, const uint32_t* challenges, size_t n_challenges, AirMode mode) {
+  TraceProgram tp;
+  if (mats.empty()) fail(P3R_EINVAL, "n_mats == 0: no trace to evaluate the program on");
+  if ((n_public && !publics) || (n_challenges && !challenges)) fail(P3R_EINVAL, "public_values or challenges is NULL");
+  const size_t h = tp.h = mats[0]->h;
+  tp.log_h = air_trace_log_height(h, PP::TWO_ADICITY);   // a power of two within the field's two-adicity
+  tp.widths.resize(mats.size());
+  for (size_t m = 0; m < mats.size(); ++m) {
+    if (mats[m]->h != h) fail(P3R_EINVAL, "matrix %zu has %zu rows, matrix 0 has %zu: the traces of one table share a height", m, mats[m]->h, h);
+    tp.widths[m] = mats[m]->w;
+    tp.n_cols += tp.widths[m];
+  }
+  if (tp.n_cols > 0x7fffffffu) fail(P3R_EINVAL, "too many columns");
+  for (size_t k = 0; k < n_public; ++k)
+    if (publics[k] >= PP::P) fail(P3R_EINVAL, "non-canonical public value %zu", k);
+  for (size_t k = 0; k < n_challenges * DC; ++k)
+    if (challenges[k] >= PP::P) fail(P3R_EINVAL, "non-canonical word %zu of challenge %zu", k % DC, k / DC);
+  tp.plan = air_plan(prog, n_insns, tp.widths.data(), tp.widths.size(), DC, PP::P, n_public, n_challenges, P3R_AIR_MAX_LIVE, mode);
+  tp.lds = tp.plan.lds_bytes(DC);
+  if (tp.lds > kAirMaxLdsBytes) fail(P3R_EUNSUPPORTED, "the program's slot file (%zu bytes) does not fit the LDS", tp.lds);
+  return tp;
+}
+
+// The instruction stream, the challenge table and the column pointers of one launch as one upload, after `head` bytes the
+// caller fills (answer words, a job): where each part lies in the blob.
+struct ProgramBlob {
+  size_t off_insns, off_consts, off_cols;
+  std::vector<unsigned char> host;
+  DevBuf dev;
+  ProgramBlob(size_t head, const AirCompiled& code, const std::vector<const p3r_dmat*>& mats, size_t n_cols) {
+    std::vector<const uint32_t*> cols;
+    cols.reserve(n_cols);
+    for (const p3r_dmat* m : mats)
+      for (size_t c = 0; c < m->w; ++c) cols.push_back(m->d + c * m->h);
+    off_insns = (head + 15) / 16 * 16;
+    off_consts = off_insns + code.insns.size() * sizeof(AirDevInsn);
+    off_cols = (off_consts + code.ext_consts.size() * 4 + 7) / 8 * 8;
+    host.assign(off_cols + cols.size() * sizeof(void*), 0);
+    memcpy(host.data() + off_insns, code.insns.data(), code.insns.size() * sizeof(AirDevInsn));
+    if (!code.ext_consts.empty()) memcpy(host.data() + off_consts, code.ext_consts.data(), code.ext_consts.size() * 4);
+    if (!cols.empty()) memcpy(host.data() + off_cols, cols.data(), cols.size() * sizeof(void*));
+    dev.alloc((host.size() + 3) / 4);
+  }
+  unsigned char* base() const { return reinterpret_cast<unsigned char*>(dev.p); }
+  const AirDevInsn* insns() const { return reinterpret_cast<const AirDevInsn*>(base() + off_insns); }
+  const uint32_t* ext_consts() const { return reinterpret_cast<const uint32_t*>(base() + off_consts); }
+  const uint32_t* const* cols() const { return reinterpret_cast<const uint32_t* const*>(base() + off_cols); }
+  void upload(p3r_ctx* ctx) { P3R_HIP(ctx->stage.upload(ctx->stream, dev.p, host.data(), host.size())); }
+};
+
 // The lookup-program seam (p3r_logup_program_dmat): the LogUp gadget of p3_lookup for interactions the caller brings as
 // data.  k_logup_program writes the fraction columns and each row's total; the running sum and the table's sum are the
 // prover's own three-mode scan k_ef_scan over a LogupJob of one job.  The call waits for the stream: the sum goes to the
@@ -122,25 +188,11 @@ std::unique_ptr<p3r_dmat> logup_program_dc(p3r_ctx* ctx, const p3r_air_insn* pro
   // ---- everything that is refused, before anything is allocated or launched
   if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the lookup-program seam does not serve zk contexts (their traces are randomised and their domains doubled)");
   if (!sum_out) fail(P3R_EINVAL, "sum_out is NULL");
-  if (mats.empty()) fail(P3R_EINVAL, "n_mats == 0: no trace to evaluate the program on");
-  if ((n_public && !publics) || (n_challenges && !challenges)) fail(P3R_EINVAL, "public_values or challenges is NULL");
-  const size_t h = mats[0]->h;
-  const int log_h = air_trace_log_height(h, PP::TWO_ADICITY);   // a power of two within the field's two-adicity
-  std::vector<size_t> widths(mats.size());
-  size_t n_cols = 0;
-  for (size_t m = 0; m < mats.size(); ++m) {
-    if (mats[m]->h != h) fail(P3R_EINVAL, "matrix %zu has %zu rows, matrix 0 has %zu: the traces of one table share a height", m, mats[m]->h, h);
-    widths[m] = mats[m]->w;
-    n_cols += widths[m];
-  }
-  if (n_cols > 0x7fffffffu) fail(P3R_EINVAL, "too many columns");
-  for (size_t k = 0; k < n_public; ++k)
-    if (publics[k] >= PP::P) fail(P3R_EINVAL, "non-canonical public value %zu", k);
-  for (size_t k = 0; k < n_challenges * DC; ++k)
-    if (challenges[k] >= PP::P) fail(P3R_EINVAL, "non-canonical word %zu of challenge %zu", k % DC, k / DC);
-  const AirPlan plan = air_plan(prog, n_insns, widths.data(), widths.size(), DC, PP::P, n_public, n_challenges, P3R_AIR_MAX_LIVE, AIR_MODE_LOOKUP);
-  const size_t lds = plan.lds_bytes(DC);
-  if (lds > kAirMaxLdsBytes) fail(P3R_EUNSUPPORTED, "the program's slot file (%zu bytes) does not fit the LDS", lds);
+  const TraceProgram tp = trace_program<PP, DC>(prog, n_insns, mats, publics, n_public, challenges, n_challenges, AIR_MODE_LOOKUP);
+  const AirPlan& plan = tp.plan;
+  const std::vector<size_t>& widths = tp.widths;
+  const size_t h = tp.h, n_cols = tp.n_cols, lds = tp.lds;
+  const int log_h = tp.log_h;
   const size_t G = plan.lookup.n_columns;
   if (G > (0x7fffffffu / DC) - 1) fail(P3R_EINVAL, "too many auxiliary columns");
 
@@ -210,6 +262,281 @@ std::unique_ptr<p3r_dmat> logup_program_dc(p3r_ctx* ctx, const p3r_air_insn* pro
   return out;
 }
 
+// The constraint check (p3r_check_program_dmat): DebugConstraintBuilder / check_air_satisfies for constraints the caller
+// brings as data.  One launch of k_check_program; the device answers with a first failing row and a count per constraint,
+// from which the report is derived here.  A trace that fails is a result, not an error.  Waits for the stream.
+template <class PP, int DC>
+void check_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
+                      const uint32_t* publics, size_t n_public, const uint32_t* challenges, size_t n_challenges, p3r_check_report* report,
+                      uint32_t* first_row_out, uint64_t* n_failed_out) {
+  // ---- everything that is refused, before anything is allocated or launched
+  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the constraint check does not serve zk contexts (their traces are randomised and their domains doubled)");
+  if (!report) fail(P3R_EINVAL, "report is NULL");
+  const TraceProgram tp = trace_program<PP, DC>(prog, n_insns, mats, publics, n_public, challenges, n_challenges, AIR_MODE_CONSTRAINTS);
+  const size_t nc = tp.plan.info.n_constraints;
+
+  // ---- the launch
+  const AirCompiled code = air_compile<PP>(tp.plan, prog, n_insns, tp.widths.data(), tp.widths.size(), DC, publics, challenges);
+  // the answer leads the upload: a count (two words) per constraint, zero, then a first row per constraint, "none"
+  ProgramBlob blob(12 * nc, code, mats, tp.n_cols);
+  memset(blob.host.data() + 8 * nc, 0xff, 4 * nc);
+  blob.upload(ctx);
+  AirCheckArgs a{};
+  a.insns = blob.insns();
+  a.ext_consts = blob.ext_consts();
+  a.cols = blob.cols();
+  a.n_failed = reinterpret_cast<unsigned long long*>(blob.base());
+  a.first_row = blob.dev.p + 2 * nc;
+  a.n_insns = (uint32_t)code.insns.size();
+  a.log_h = tp.log_h;
+  {
+    ProfScope ps(ctx, "check_program");
+    // rows r < h of every input column are read; constraint k < nc - the ASSERTs of the stream, which air_plan counted -
+    // touches n_failed[k] and first_row[k]: all inside the allocations above
+    const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
+    if (tp.lds > 48 * 1024)
+      P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_check_program<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)kAirMaxLdsBytes));
+    hipLaunchKernelGGL((k_check_program<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, ctx->stream, a);
+  }
+  P3R_HIP(hipGetLastError());
+  std::vector<uint32_t> answer(3 * nc);
+  P3R_HIP(fetch_small(ctx, blob.dev.p, answer.size(), answer.data()));   // waits for the stream
+  *report = p3r_check_report{0, 0xffffffffu, 0xffffffffu};
+  for (size_t k = 0; k < nc; ++k) {
+    const uint64_t failed = answer[2 * k] | ((uint64_t)answer[2 * k + 1] << 32);
+    const uint32_t first = answer[2 * nc + k];
+    report->n_failures += failed;
+    if (first < report->first_row) {   // constraints in ascending order: the smallest of the row stays
+      report->first_row = first;
+      report->first_constraint = (uint32_t)k;
+    }
+    if (first_row_out) first_row_out[k] = first;
+    if (n_failed_out) n_failed_out[k] = failed;
+  }
+}
+
+// ---- the lookup check (p3r_lookup_check_dmat): p3_lookup::debug_util::check_lookups over lookup programs.
+// Slots: term t of row r of instance p is slot base_p + r * n_terms_p + t; a slot whose multiplicity is not zero is a
+// record, and ascending slots are record order.  After k_lookup_records the pass is the primitives of
+// device_prims.hip.h and the few kernels below, which index by what those wrote.
+
+// words [DC][n_slots] of the records at sorted positions i - 1 and i differ: i opens a key's run
+template <int DC>
+__global__ void __launch_bounds__(prims::kPB) k_lookup_heads(const uint32_t* __restrict__ den, size_t n_slots, const uint32_t* __restrict__ order,
+                                                             size_t n, uint32_t* __restrict__ head) {
+  const size_t i = (size_t)blockIdx.x * prims::kPB + threadIdx.x;
+  if (i >= n) return;
+  uint32_t differ = i == 0;
+  if (i) {
+    const size_t s = order[i], s_prev = order[i - 1];
+#pragma unroll
+    for (int k = 0; k < DC; ++k) differ |= den[(size_t)k * n_slots + s] != den[(size_t)k * n_slots + s_prev];
+  }
+  head[i] = differ ? 1u : 0u;
+}
+// the multiplicity word of coefficient k at a sorted position: what the exclusive sums run over
+struct SortedWord {
+  const uint32_t* words;   // one coefficient's [n_slots]
+  const uint32_t* order;
+  __device__ uint64_t operator()(size_t i) const { return words[order[i]]; }
+};
+// A key's run in the sorted records: head_rank[i] = the heads before position i and heads[j] = position of head j
+// (select_marked over the head marks; the number of heads stands at head_rank[n]); prefix[k][i] = the canonical words of
+// coefficient k before position i, n + 1 of them (ranks_of).
+template <int DC>
+struct LookupRuns {
+  const uint32_t* head_rank;
+  const uint32_t* heads;
+  const uint64_t* prefix[DC];
+  size_t n;
+  // position one past the run that position `i` opens
+  __device__ size_t end_of(size_t i) const {
+    const uint32_t j = head_rank[i];
+    return j + 1 < head_rank[n] ? heads[j + 1] : n;
+  }
+  // at most 2^28 words below 2^31 per coefficient: the sums stay below 2^59
+  __device__ uint32_t net(int k, size_t i, size_t end, uint32_t p) const { return (uint32_t)((prefix[k][end] - prefix[k][i]) % p); }
+};
+template <int DC>
+__global__ void __launch_bounds__(prims::kPB) k_lookup_flag(LookupRuns<DC> runs, const uint32_t* __restrict__ head, uint32_t p,
+                                                            uint32_t* __restrict__ flag) {
+  const size_t i = (size_t)blockIdx.x * prims::kPB + threadIdx.x;
+  if (i >= runs.n) return;
+  uint32_t unbalanced = 0;
+  if (head[i]) {
+    const size_t end = runs.end_of(i);
+#pragma unroll
+    for (int k = 0; k < DC; ++k) unbalanced |= runs.net(k, i, end, p);
+  }
+  flag[i] = unbalanced ? 1u : 0u;
+}
+constexpr int kImbalanceWords = 2 + 2 * kMaxAirDC;   // first slot, records, denominator, net
+// entry j < n_out of the answer: the unbalanced key whose first record is slot first_slot[j], at sorted position pos[j]
+template <int DC>
+__global__ void __launch_bounds__(prims::kPB) k_lookup_report(LookupRuns<DC> runs, const uint32_t* __restrict__ den, size_t n_slots,
+                                                              const uint32_t* __restrict__ first_slot, const uint32_t* __restrict__ pos,
+                                                              size_t n_out, uint32_t p, uint32_t* __restrict__ out) {
+  const size_t j = (size_t)blockIdx.x * prims::kPB + threadIdx.x;
+  if (j >= n_out) return;
+  const size_t i = pos[j], s = first_slot[j], end = runs.end_of(i);
+  uint32_t* o = out + j * kImbalanceWords;
+  o[0] = (uint32_t)s;
+  o[1] = (uint32_t)(end - i);
+#pragma unroll
+  for (int k = 0; k < DC; ++k) {
+    o[2 + k] = den[(size_t)k * n_slots + s];
+    o[2 + kMaxAirDC + k] = runs.net(k, i, end, p);
+  }
+#pragma unroll
+  for (int k = DC; k < kMaxAirDC; ++k) o[2 + k] = o[2 + kMaxAirDC + k] = 0u;
+}
+
+// the marked items of marks[0 .. n): their number (one blocking read) and their indices in ascending order
+inline DevBuf marked_list(p3r_ctx* ctx, const uint32_t* marks, size_t n, DevBuf& rank /* n + 1 */, size_t* count) {
+  *count = prims::select_marked_count(ctx->stream, marks, n, rank.p);
+  DevBuf list(*count);
+  if (*count) hipLaunchKernelGGL(prims::k_compact_marked, dim3(prims::blocks_of(n)), dim3(prims::kPB), 0, ctx->stream, marks, rank.p, n, list.p);
+  P3R_HIP(hipGetLastError());
+  return list;
+}
+
+template <class PP, int DC>
+void lookup_check_dc(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges,
+                     p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out) {
+  // ---- everything that is refused, before anything is allocated or launched
+  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the lookup check does not serve zk contexts (their traces are randomised and their domains doubled)");
+  if (insts.empty()) fail(P3R_EINVAL, "n_inst == 0: no table on the bus");
+  if (!n_unbalanced_out) fail(P3R_EINVAL, "n_unbalanced_out is NULL");
+  if (cap && !out) fail(P3R_EINVAL, "out is NULL with cap > 0");
+  std::vector<TraceProgram> tps;
+  std::vector<size_t> base(1, 0);   // first slot of every instance, and the total
+  for (size_t p = 0; p < insts.size(); ++p) {
+    const LookupCheckInstance& in = insts[p];
+    try {
+      tps.push_back(trace_program<PP, DC>(in.prog, in.n_insns, in.mats, in.publics, in.n_public, challenges, n_challenges, AIR_MODE_LOOKUP));
+    } catch (const Error& e) {
+      fail(e.code, "instance %zu: %s", p, e.what());
+    }
+    const size_t slots = tps[p].h * tps[p].plan.lookup.n_terms;   // below 2^27 * 2^31
+    if (slots > P3R_LOOKUP_CHECK_MAX_RECORDS || base[p] + slots > P3R_LOOKUP_CHECK_MAX_RECORDS)
+      fail(P3R_EUNSUPPORTED, "more than P3R_LOOKUP_CHECK_MAX_RECORDS (2^28) term slots: rows x terms, summed over the instances");
+    base.push_back(base[p] + slots);
+  }
+  const size_t S = base.back();
+  hipStream_t s = ctx->stream;
+
+  // ---- the records: one launch per instance
+  DevBuf den((size_t)DC * S), mul((size_t)DC * S), mark(S);
+  {
+    ProfScope ps(ctx, "lookup_check_records");
+    for (size_t p = 0; p < insts.size(); ++p) {
+      const LookupCheckInstance& in = insts[p];
+      const TraceProgram& tp = tps[p];
+      const AirCompiled code = air_compile<PP>(tp.plan, in.prog, in.n_insns, tp.widths.data(), tp.widths.size(), DC, in.publics, challenges);
+      ProgramBlob blob(0, code, in.mats, tp.n_cols);
+      blob.upload(ctx);
+      AirRecordArgs a{};
+      a.insns = blob.insns();
+      a.ext_consts = blob.ext_consts();
+      a.cols = blob.cols();
+      a.den = den.p;
+      a.mul = mul.p;
+      a.mark = mark.p;
+      a.n_slots = S;
+      a.base = base[p];
+      a.n_terms = tp.plan.lookup.n_terms;
+      a.n_insns = (uint32_t)code.insns.size();
+      a.log_h = tp.log_h;
+      // rows r < h of every input column are read; slot base + r * n_terms + t with r < h and t < n_terms - the TERMs of
+      // the stream, which air_plan counted - lies in [base_p, base_p+1), so below S: words k * S + slot < DC * S of den and
+      // mul and word slot of mark.  Every slot of the instance is written: nothing is read uninitialised afterwards.
+      const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
+      if (tp.lds > 48 * 1024)
+        P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lookup_records<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)kAirMaxLdsBytes));
+      hipLaunchKernelGGL((k_lookup_records<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, s, a);
+      P3R_HIP(hipGetLastError());
+      // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
+    }
+  }
+
+  // ---- the records among the slots, ordered by key
+  *n_unbalanced_out = 0;
+  size_t n = 0;
+  DevBuf slot_rank(S + 1);
+  DevBuf order = marked_list(ctx, mark.p, S, slot_rank, &n);   // order[i]: the slot of the record at position i
+  slot_rank.release();
+  mark.release();
+  if (!n) return;
+  const unsigned blocks_n = prims::blocks_of(n);
+  {
+    ProfScope ps(ctx, "lookup_check_sort");
+    // least significant word first, every word a canonical residue below 2^31; the sort is stable, so records of one key
+    // stay in record order and the first of a run is the key's first record
+    DevBuf keys(n), keys_sorted(n), order_next(n);
+    for (int k = 0; k < DC; ++k) {
+      hipLaunchKernelGGL(prims::k_gather_u32, dim3(blocks_n), dim3(prims::kPB), 0, s, den.p + (size_t)k * S, order.p, n, keys.p);
+      prims::sort_pairs(s, keys.p, keys_sorted.p, order.p, order_next.p, n, 31);
+      std::swap(order, order_next);
+    }
+    P3R_HIP(hipGetLastError());
+  }
+  uint64_t n_unbalanced = 0;
+  std::vector<uint32_t> answer;
+  {
+    ProfScope ps(ctx, "lookup_check_sums");
+    // ---- the runs of equal keys and their sums
+    DevBuf head(n), head_rank(n + 1), heads(n), flag(n), flag_rank(n + 1);
+    hipLaunchKernelGGL((k_lookup_heads<DC>), dim3(blocks_n), dim3(prims::kPB), 0, s, den.p, S, order.p, n, head.p);
+    prims::select_marked(s, head.p, n, head_rank.p, heads.p);   // as many heads as keys: the first of them are written
+    DevBuf prefix[DC];
+    LookupRuns<DC> runs{};
+    runs.head_rank = head_rank.p;
+    runs.heads = heads.p;
+    runs.n = n;
+    for (int k = 0; k < DC; ++k) {
+      prefix[k].alloc(2 * (n + 1));
+      uint64_t* pk = reinterpret_cast<uint64_t*>(prefix[k].p);
+      prims::ranks_of<uint64_t>(s, SortedWord{mul.p + (size_t)k * S, order.p}, n, pk);
+      runs.prefix[k] = pk;
+    }
+    hipLaunchKernelGGL((k_lookup_flag<DC>), dim3(blocks_n), dim3(prims::kPB), 0, s, runs, head.p, PP::P, flag.p);
+    P3R_HIP(hipGetLastError());
+    // ---- the unbalanced heads, ordered by their first record
+    size_t nu = 0;
+    DevBuf pos = marked_list(ctx, flag.p, n, flag_rank, &nu);   // sorted positions of the unbalanced heads
+    n_unbalanced = nu;
+    const size_t n_out = std::min(cap, nu);
+    if (n_out) {
+      DevBuf first_slot(nu), first_sorted(nu), pos_sorted(nu), d_answer(n_out * kImbalanceWords);
+      hipLaunchKernelGGL(prims::k_gather_u32, dim3(prims::blocks_of(nu)), dim3(prims::kPB), 0, s, order.p, pos.p, nu, first_slot.p);
+      prims::sort_pairs(s, first_slot.p, first_sorted.p, pos.p, pos_sorted.p, nu, 32);
+      // j < n_out <= nu entries of first_sorted / pos_sorted are read, n_out * kImbalanceWords words written
+      hipLaunchKernelGGL((k_lookup_report<DC>), dim3(prims::blocks_of(n_out)), dim3(prims::kPB), 0, s, runs, den.p, S, first_sorted.p,
+                         pos_sorted.p, n_out, PP::P, d_answer.p);
+      P3R_HIP(hipGetLastError());
+      answer.resize(n_out * kImbalanceWords);
+      P3R_HIP(fetch_small(ctx, d_answer.p, answer.size(), answer.data()));   // waits for the stream
+    }
+  }
+  *n_unbalanced_out = n_unbalanced;
+  for (size_t j = 0; j * kImbalanceWords < answer.size(); ++j) {   // at most `cap` entries: no loop over records
+    const uint32_t* o = answer.data() + j * kImbalanceWords;
+    const size_t p = (size_t)(std::upper_bound(base.begin(), base.end(), (size_t)o[0]) - base.begin()) - 1;
+    const uint32_t n_terms = tps[p].plan.lookup.n_terms;
+    p3r_lookup_imbalance& e = out[j];
+    e.instance = (uint32_t)p;
+    e.row = (uint32_t)((o[0] - base[p]) / n_terms);
+    e.term = (uint32_t)((o[0] - base[p]) % n_terms);
+    e.n_records = o[1];
+    for (int k = 0; k < kMaxAirDC; ++k) {
+      e.denominator[k] = o[2 + k];
+      e.net[k] = o[2 + kMaxAirDC + k];
+    }
+  }
+}
+
 }  // namespace
 
 template <class PP>
@@ -238,6 +565,28 @@ std::vector<std::unique_ptr<p3r_dmat>> quotient_program(p3r_ctx* ctx, const p3r_
                                     n_challenges, alpha);
 }
 
+template <class PP>
+void check_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats, const uint32_t* publics,
+                   size_t n_public, const uint32_t* challenges, size_t n_challenges, p3r_check_report* report, uint32_t* first_row_out,
+                   uint64_t* n_failed_out) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>)
+      return check_program_dc<PP, 5>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, report, first_row_out, n_failed_out);
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  check_program_dc<PP, 4>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, report, first_row_out, n_failed_out);
+}
+
+template <class PP>
+void lookup_check(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges,
+                  p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>) return lookup_check_dc<PP, 5>(ctx, insts, challenges, n_challenges, out, cap, n_unbalanced_out);
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  lookup_check_dc<PP, 4>(ctx, insts, challenges, n_challenges, out, cap, n_unbalanced_out);
+}
+
 #define P3R_AIR_INSTANCE(PP)                                                                                                     \
   template std::vector<std::unique_ptr<p3r_dmat>> quotient_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t,                    \
                                                                        const std::vector<const p3r_dmat*>&, uint32_t, uint32_t, \
@@ -252,5 +601,13 @@ P3R_AIR_INSTANCE(BabyBearParams)
 P3R_LOGUP_INSTANCE(KoalaBearParams)
 P3R_LOGUP_INSTANCE(BabyBearParams)
 #undef P3R_LOGUP_INSTANCE
+#define P3R_CHECK_INSTANCE(PP)                                                                                                            \
+  template void check_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&, const uint32_t*, size_t,    \
+                                  const uint32_t*, size_t, p3r_check_report*, uint32_t*, uint64_t*);                                      \
+  template void lookup_check<PP>(p3r_ctx*, const std::vector<LookupCheckInstance>&, const uint32_t*, size_t, p3r_lookup_imbalance*,        \
+                                 size_t, uint64_t*);
+P3R_CHECK_INSTANCE(KoalaBearParams)
+P3R_CHECK_INSTANCE(BabyBearParams)
+#undef P3R_CHECK_INSTANCE
 
 }  // namespace p3r

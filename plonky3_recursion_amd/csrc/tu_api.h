@@ -127,6 +127,31 @@ std::unique_ptr<p3r_dmat> logup_program(p3r_ctx* ctx, const p3r_air_insn* prog, 
                                         const uint32_t* publics, size_t n_public, const uint32_t* challenges, size_t n_challenges,
                                         uint32_t* sum_out);
 
+// check_air_satisfies for a caller's AIR (tu_air.hip): the constraint program `prog` on every row of the TRACES `mats`
+// (one height h, natural order) with 0 / 1 selectors.  first_row_out / n_failed_out (host, n_constraints each, may be
+// null): the smallest row in which constraint k does not vanish (0xffffffff: none) and the number of such rows; the
+// report is derived from them.  A failing trace is a result.  Refuses before anything is allocated or launched; waits
+// for the stream.
+template <class PP>
+void check_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats, const uint32_t* publics,
+                   size_t n_public, const uint32_t* challenges, size_t n_challenges, p3r_check_report* report, uint32_t* first_row_out,
+                   uint64_t* n_failed_out);
+
+// check_lookups for a caller's lookup programs (tu_air.hip): the terms of every instance with a non-zero multiplicity are
+// records keyed by their denominator; a key whose multiplicities do not sum to zero is unbalanced.  Writes their number
+// and the min(cap, number) of them whose first records come earliest.  Refuses before anything is allocated or launched;
+// waits for the stream.
+struct LookupCheckInstance {
+  const p3r_air_insn* prog;
+  size_t n_insns;
+  std::vector<const p3r_dmat*> mats;
+  const uint32_t* publics;
+  size_t n_public;
+};
+template <class PP>
+void lookup_check(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges,
+                  p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out);
+
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>
 void launch_logup_aux(p3r_ctx* ctx, unsigned blocks, const LogupJob* d_jobs, int n_jobs, const LookupChT<DC>& lc);

@@ -630,6 +630,59 @@ class Context:
                                                    total.ctypes.data_as(_lib.u32p)))
         return DeviceMatrix(self, self.ptr(out.value)), total
 
+    # ---- is the caller's trace right: unsatisfied constraints and unbalanced lookups, located
+    def check_device(self, program, dmats, public_values=(), challenges=()):
+        """check_air_satisfies for the constraint `program` (an AirBuilder or an (n, 3) array of (op, a, b)) over the TRACES
+        `dmats`: one height h, natural row order, not LDEs; the next row of r is (r + 1) mod h and the selectors are 0 / 1
+        (is_first_row = [r == 0], is_last_row = [r == h - 1], is_transition = [r != h - 1]).  Returns a dict: n_failures (the
+        (row, constraint) pairs whose value is not zero), first_row (the smallest failing row; 0xffffffff: the trace
+        satisfies the program), first_constraint (the smallest failing constraint in that row), and per constraint the arrays
+        first_row_of (uint32; 0xffffffff: it holds everywhere) and n_failed_of (uint64).  A failing trace is a result, not an
+        error.  Waits for the device."""
+        dc = self.challenge_degree
+        arr, n = _air_insns(program)
+        prog = program.program() if isinstance(program, AirBuilder) else np.asarray(program).reshape(-1, 3)
+        n_constraints = int(np.count_nonzero(prog[:, 0] == _lib.P3R_AIR_ASSERT_ZERO)) if len(prog) else 0
+        mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+        pv, pvp = _u32(np.asarray(public_values, dtype=np.uint32).reshape(-1))
+        ch, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
+        first = np.zeros(max(1, n_constraints), dtype=np.uint32)
+        failed = np.zeros(max(1, n_constraints), dtype=np.uint64)
+        report = _lib.P3rCheckReport()
+        self.check(self.lib.p3r_check_program_dmat(self.h, arr, n, mats, len(dmats), pvp, pv.size, chp, len(ch), C.byref(report),
+                                                   first.ctypes.data_as(_lib.u32p), failed.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return {"n_failures": int(report.n_failures), "first_row": int(report.first_row), "first_constraint": int(report.first_constraint),
+                "first_row_of": first[:n_constraints], "n_failed_of": failed[:n_constraints]}
+
+    def lookup_check_device(self, instances, challenges=(), cap=16):
+        """check_lookups over the tables of a bus.  `instances`: (program, dmats) or (program, dmats, public_values) each -
+        a lookup program as logup_device takes it and its traces (one height per instance); `challenges` ((n, DC) canonical
+        words) are shared.  Every term with a non-zero multiplicity is a record keyed by its denominator value; a key whose
+        multiplicities do not sum to zero is unbalanced.  Returns (n_unbalanced, entries): the number of unbalanced keys
+        and, for the min(cap, n_unbalanced) of them whose first records come earliest in (instance, row, term) order, a
+        dict of instance, row, term (the key's first record), n_records, denominator and net (DC canonical words each).
+        Waits for the device."""
+        dc = self.challenge_degree
+        ch, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
+        arr = (_lib.P3rLookupInstance * max(1, len(instances)))()
+        keep = []   # what the structs point to
+        for k, inst in enumerate(instances):
+            program, dmats = inst[0], inst[1]
+            insns, n = _air_insns(program)
+            mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+            pv, pvp = _u32(np.asarray(inst[2] if len(inst) > 2 else (), dtype=np.uint32).reshape(-1))
+            keep.append((insns, mats, pv))
+            arr[k].prog, arr[k].n_insns = insns, n
+            arr[k].mats, arr[k].n_mats = mats, len(dmats)
+            arr[k].public_values, arr[k].n_public = pvp, pv.size
+        out = (_lib.P3rLookupImbalance * max(1, int(cap)))()
+        count = C.c_uint64()
+        self.check(self.lib.p3r_lookup_check_dmat(self.h, arr, len(instances), chp, len(ch), out, int(cap), C.byref(count)))
+        entries = [{"instance": int(e.instance), "row": int(e.row), "term": int(e.term), "n_records": int(e.n_records),
+                    "denominator": [int(v) for v in e.denominator[:dc]], "net": [int(v) for v in e.net[:dc]]}
+                   for e in out[:min(int(cap), count.value)]]
+        return count.value, entries
+
     # ---- the rest of prove_fri: challenger, commit-phase leaf view, final polynomial, schedule, and their composition
     def challenger(self):
         """A fresh DuplexChallenger over the context's width-16 Poseidon2 constants (p3r_challenger)."""
