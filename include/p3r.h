@@ -50,7 +50,9 @@ enum {
   P3R_EHIP = -3,     /* HIP runtime error */
   P3R_ENOMEM = -4,
   P3R_EUNSUPPORTED = -5, /* reference: BatchStarkProverError::UnsupportedDegree */
-  P3R_EBUFFER = -6   /* caller buffer too small */
+  P3R_EBUFFER = -6,  /* caller buffer too small */
+  P3R_EVERIFY = -7   /* a well-formed proof that a verifier rejects (the FRI verifier seam; p3r_verify_batch, the older
+                      * entry, keeps reporting a rejection as P3R_EINVAL with the reason in its error buffer) */
 };
 
 enum { P3R_FIELD_KOALA_BEAR = 0, P3R_FIELD_BABY_BEAR = 1 };
@@ -514,6 +516,96 @@ int p3r_fri_final_poly_dmat(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_fina
                             uint32_t* coeffs_out /* 2^log_final_poly_len x DC */);
 int p3r_fri_log_arity(const p3r_ctx* ctx, size_t phase, int log_cur, int log_final, int log_next_input /* -1: none */);
 
+/* ---- the verifier's side of the FRI seam: p3_fri::verifier::verify_fri on the host ----
+ *
+ * Functions are only added: P3R_ABI_VERSION stays as it is (no struct and no existing entry changes meaning).
+ *
+ * Host code, no context and no device: a proof made by the calls of the two sections above (Context.prove_fri,
+ * p3r::prove_fri) is checked on a machine without a GPU.  The in-tree statement is recursion/src/pcs/fri/verifier.rs:
+ * 1371-1838; the code is the FRI part of p3r_verify_batch (csrc/fri_verify.h), which both entries run.
+ *
+ * p3r_challenger_create_host == p3r_challenger_create from a configuration alone, as p3r_mmcs_verify takes its
+ *                            parameters: the same handle, the same sponge over cfg->poseidon2_rc (NULL: the defaults), the
+ *                            same behaviour in every p3r_challenger_* entry, _clone and _free included.  Only
+ *                            p3r_challenger_grind refuses it (P3R_EINVAL, state unchanged): the search runs on a device.
+ *                            The message of that refusal is where p3r_challenger_grind's always is: p3r_last_error of the
+ *                            ctx it was given (of NULL for a NULL ctx); every other refusal on a host handle is
+ *                            p3r_last_error(NULL)'s.
+ *                            NULL on failure, with the message in p3r_last_error(NULL): a NULL cfg, an ABI mismatch, an
+ *                            unknown field or challenge degree, constants of the wrong length or not canonical.
+ * p3r_fri_log_arity_cfg      == p3r_fri_log_arity with the max_log_arity and fri_log_arities of a configuration.
+ *
+ * p3r_fri_proof_view: what prove_fri returns, every array a pointer and a length in WORDS (canonical), n_phases =
+ * log_arities_len:
+ *   log_max_height              log2 of the tallest input's height: the bits of a query index
+ *   commit_caps                 n_phases x 2^cap_height x 8: the caps of the commit phases, in order
+ *   commit_pow                  n_phases: the commit proof-of-work witnesses (0 where commit_pow_bits == 0)
+ *   log_arities                 n_phases bytes: log2 of every phase's arity
+ *   final_poly                  2^log_final_poly_len x DC: the coefficients in natural order
+ *   query_pow                   the query proof-of-work witness
+ *   n_queries, openings         n_queries x n_phases p3r_fri_phase_opening_view, query-major.  For query index i and
+ *                               phase p over a tree of 2^L rows (L = log_max_height - the arities up to and including p):
+ *     row       (2^log_arity - 1) x DC: the opened leaf row WITHOUT the element at (i >> earlier arities) & (2^log_arity - 1)
+ *               - the proof's sibling_values; the verifier puts its own folded value there
+ *     salts     mmcs_salt_elems words under a hiding MMCS, else length 0
+ *     siblings  proof_len x 8, as p3r_mmcs_open_batch wrote them for the phase's tree (binary: L - cap_height digests;
+ *               arity 4: step - 1 per level)
+ * p3r_fri_input_view: one per input height, tallest first, strictly decreasing, the first at log_max_height (as
+ * prove_fri takes its inputs): `values` = n_queries x DC, entry q the reduced opening of that height at
+ * index_q >> (log_max_height - log_height).
+ *
+ * p3r_fri_verify_transcript == the transcript of verify_fri up to the query indices, which exist only after it: per phase
+ *                            the cap is observed, the commit proof of work checked and beta sampled; the final polynomial
+ *                            and the log arities are observed (as prove_fri observes them); the query proof of work is
+ *                            checked; n_queries indices of log_max_height bits are sampled.  betas_out: n_phases x DC,
+ *                            indices_out: n_queries.  On P3R_OK `ch` is where prove_fri left the prover's challenger; on
+ *                            any other result it has not moved.  Without the input heights the schedule is checked as far
+ *                            as it can be: every arity in 1 .. max_log_arity (the explicit schedule's entry where there is
+ *                            one) and their sum log_max_height - log_final_poly_len - log_blowup.
+ * p3r_fri_verify         == verify_fri.  `ch` is the challenger BEFORE the proof (a clone of the one the transcript entry
+ *                            is given): the replay is done again, then every query is checked:
+ *                              - the log arities are exactly what p3r_fri_log_arity gives for the input heights;
+ *                              - the fold chain starts from the tallest input's value and uses the arithmetic of
+ *                                p3r_fri_fold_dmat: fold2 with beta, beta^2, beta^4, .., and beta^(2^log_arity) * input
+ *                                added at the height where an input joins;
+ *                              - every phase's row, with the folded value put back, opens the phase's cap under the
+ *                                configuration's MMCS (arity 2 or 4, cap_height, salts);
+ *                              - the end of the chain is the final polynomial at the query's point.
+ *                            On P3R_OK `ch` is left as the transcript entry leaves it; otherwise it has not moved.
+ * Results.  P3R_OK: accepted.  P3R_EVERIFY: rejected, the message (p3r_last_error(NULL)) names the rule and the place -
+ * "commit proof-of-work of phase 1", "query 2: final polynomial mismatch", "FRI commit phase 0 of query 1: Merkle root
+ * mismatch", a log arity the schedule does not give, a number of phases or queries other than the configuration's.
+ * P3R_EINVAL: malformed - a NULL pointer with a non-zero length, a non-canonical word, a length that does not fit the
+ * configuration and the schedule, an input height above log_max_height, repeated or out of order, no input at
+ * log_max_height, a challenger of another field or challenge degree.  P3R_EUNSUPPORTED: zk = 1 (the hiding PCS's opening
+ * proof is out of scope, as in the program seams); the hiding MMCS (mmcs_salt_elems > 0) is served.  No call reads
+ * outside the lengths it was given. */
+typedef struct p3r_fri_phase_opening_view {
+  const uint32_t* row;      size_t row_len;
+  const uint32_t* salts;    size_t salts_len;
+  const uint32_t* siblings; size_t siblings_len;
+} p3r_fri_phase_opening_view;
+typedef struct p3r_fri_proof_view {
+  uint32_t log_max_height;
+  uint32_t query_pow;
+  const uint32_t* commit_caps; size_t commit_caps_len;
+  const uint32_t* commit_pow;  size_t commit_pow_len;
+  const uint8_t* log_arities;  size_t log_arities_len;
+  const uint32_t* final_poly;  size_t final_poly_len;
+  const p3r_fri_phase_opening_view* openings; size_t openings_len;   /* n_queries x n_phases */
+  size_t n_queries;
+} p3r_fri_proof_view;
+typedef struct p3r_fri_input_view {
+  uint32_t log_height;
+  const uint32_t* values; size_t values_len;   /* n_queries x DC */
+} p3r_fri_input_view;
+p3r_challenger* p3r_challenger_create_host(const p3r_config* cfg);
+int p3r_fri_log_arity_cfg(const p3r_config* cfg, size_t phase, int log_cur, int log_final, int log_next_input /* -1: none */);
+int p3r_fri_verify_transcript(const p3r_config* cfg, p3r_challenger* ch, const p3r_fri_proof_view* proof,
+                              uint32_t* betas_out /* n_phases x DC */, uint32_t* indices_out /* n_queries */);
+int p3r_fri_verify(const p3r_config* cfg, p3r_challenger* ch, const p3r_fri_proof_view* proof,
+                   const p3r_fri_input_view* inputs, size_t n_inputs);
+
 /* ---- the caller's AIR: constraint programs evaluated over the quotient domain of resident LDEs ----
  *
  * Functions are only added: P3R_ABI_VERSION stays as it is.
@@ -608,6 +700,28 @@ int p3r_quotient_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_i
                               const uint32_t* public_values, size_t n_public,
                               const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
                               const uint32_t* alpha /* DC */, p3r_dmat** outs /* 2^log_quotient_degree */);
+
+/* p3r_air_program_eval == the verifier's side of a constraint program: VerifierConstraintFolder for the programs
+ * p3r_quotient_program_dmat takes, at one out-of-domain point.  Host only, no context (cfg gives the field and the
+ * challenge degree, as for p3r_air_program_info); functions are only added.
+ *   local / next     sum(widths) x DC canonical words: the opened values, one challenge-field element per trace cell, at
+ *                    zeta and at zeta * w_h (h = 2^log_height), matrices in order.  LOCAL / NEXT read the element of that
+ *                    column; LOCAL_EXT / NEXT_EXT read sum_k X^k * opened[col + k], a product in the challenge field - how a
+ *                    verifier recombines the flattened columns of a permutation trace.
+ *   selectors        the formulas above at x = zeta: is_transition = zeta - w_h^-1, is_first_row = (zeta^h - 1) / (zeta - 1),
+ *                    is_last_row = (zeta^h - 1) / (zeta - w_h^-1).
+ *   folded_out       DC words: sum_k alpha^(n-1-k) * C_k(zeta), Horner in program order.
+ *   inv_zh_out       DC words: 1 / (zeta^h - 1).  folded * inv_zh is what the quotient recombined from its chunks' openings
+ *                    must equal.
+ * Refusals (message: p3r_last_error(NULL)).  P3R_EINVAL: everything p3r_air_program_info refuses about the program; a
+ * public or challenge index out of range; a non-canonical word anywhere; a NULL pointer; log_height above the field's
+ * two-adicity; zeta == 1, zeta == w_h^-1 or zeta^h == 1 - a division by zero, so the call is refused and no wrong value
+ * is returned.  P3R_EUNSUPPORTED: zk configurations.  There is no P3R_AIR_MAX_LIVE here: the host keeps all values. */
+int p3r_air_program_eval(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
+                         const uint32_t* local /* sum(widths) x DC */, const uint32_t* next /* same */, uint32_t log_height,
+                         const uint32_t* zeta /* DC */, const uint32_t* public_values, size_t n_public,
+                         const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges, const uint32_t* alpha /* DC */,
+                         uint32_t* folded_out /* DC */, uint32_t* inv_zh_out /* DC */);
 
 /* ---- the caller's lookups: lookup programs build the permutation (LogUp) trace of resident traces ----
  *

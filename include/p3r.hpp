@@ -297,6 +297,14 @@ class AirProgram {
     if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
     return out;
   }
+  // the verifier's side: the program at an out-of-domain point from opened values (p3r::eval_at, below)
+  struct Evaluation {
+    std::vector<uint32_t> folded, inv_zh;   // DC words each: the Horner fold with alpha, 1 / (zeta^h - 1)
+  };
+  inline Evaluation eval_at(const p3r_config& cfg, const std::vector<size_t>& widths, const std::vector<uint32_t>& local,
+                            const std::vector<uint32_t>& next, uint32_t log_height, const std::vector<uint32_t>& zeta,
+                            const std::vector<uint32_t>& alpha, const std::vector<uint32_t>& public_values = {},
+                            const std::vector<uint32_t>& challenges = {}) const;
 
  private:
   std::vector<p3r_air_insn> insns_;
@@ -1144,6 +1152,167 @@ inline RecursionOutput prove_aggregation_layer(const RecursionInput& left, const
   RecursionOutput out{fresh->prover->prove_all_tables(t, fresh->prepared_circuit->circuit_prover_data())};
   if (prep_cache) *prep_cache = std::move(fresh);
   return out;
+}
+
+// ---- the verifier's side (p3r.h: p3r_challenger_create_host, p3r_fri_verify_transcript, p3r_fri_verify,
+// p3r_air_program_eval).  Host only: a p3r_config is all these take, no Context and no device.
+
+// DuplexChallenger made from a configuration alone: the same transcript as DuplexChallenger(ctx) for that configuration,
+// word for word.  It cannot grind.
+class HostChallenger {
+ public:
+  explicit HostChallenger(const p3r_config& cfg) : dc_(cfg.challenge_degree == 5 ? 5 : 4), h_(p3r_challenger_create_host(&cfg)) {
+    if (!h_) throw Error(P3R_EINVAL, p3r_last_error(nullptr));
+  }
+  HostChallenger(const HostChallenger& o) : dc_(o.dc_), h_(p3r_challenger_clone(o.h_)) {   // Clone
+    if (!h_) throw Error(P3R_EINVAL, p3r_last_error(nullptr));
+  }
+  HostChallenger& operator=(const HostChallenger&) = delete;
+  ~HostChallenger() { p3r_challenger_free(h_); }
+  void observe(uint32_t word) { observe(&word, 1); }
+  void observe(const std::vector<uint32_t>& words) { observe(words.data(), words.size()); }
+  void observe(const uint32_t* words, size_t n) { check(p3r_challenger_observe(h_, words, n)); }
+  uint32_t sample() {
+    uint32_t v = 0;
+    check(p3r_challenger_sample(h_, &v, 1));
+    return v;
+  }
+  std::vector<uint32_t> sample_ext() {
+    std::vector<uint32_t> e(dc_);
+    check(p3r_challenger_sample_ext(h_, e.data()));
+    return e;
+  }
+  uint32_t sample_bits(uint32_t bits) {
+    uint32_t v = 0;
+    check(p3r_challenger_sample_bits(h_, bits, &v));
+    return v;
+  }
+  bool check_witness(uint32_t bits, uint32_t witness) {
+    int ok = 0;
+    check(p3r_challenger_check_witness(h_, bits, witness, &ok));
+    return ok != 0;
+  }
+  p3r_challenger* raw() const { return h_; }
+
+ private:
+  static void check(int rc) {
+    if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
+  }
+  size_t dc_;
+  p3r_challenger* h_;
+};
+
+// The reduced openings of one input height at the query indices: values[q * DC ..] belongs to index_q >> (log_max_height - log_height)
+struct FriInput {
+  uint32_t log_height;
+  std::vector<uint32_t> values;   // n_queries x DC
+};
+
+namespace detail {
+// the p3r_fri_proof_view of a FriProof; `indices` say which element of every opened row is the queried one (the view
+// carries the row without it), empty: rows are passed minus element 0 (the transcript entry does not read them)
+struct FriProofView {
+  p3r_fri_proof_view view{};
+  std::vector<uint32_t> caps;
+  std::vector<uint8_t> arities;
+  std::vector<std::vector<uint32_t>> rows;
+  std::vector<p3r_fri_phase_opening_view> openings;
+  FriProofView(const FriProof& proof, size_t dc, const std::vector<uint32_t>& indices) {
+    for (const auto& c : proof.commit_phase_caps) caps.insert(caps.end(), c.begin(), c.end());
+    for (uint32_t a : proof.log_arities) arities.push_back((uint8_t)a);
+    for (size_t q = 0; q < proof.query_openings.size(); ++q) {
+      uint32_t shift = 0;
+      for (size_t ph = 0; ph < proof.query_openings[q].size(); ++ph) {
+        const FriProof::PhaseOpening& o = proof.query_openings[q][ph];
+        const size_t n = o.row.size() / dc;
+        size_t pos = 0;
+        if (q < indices.size() && ph < proof.log_arities.size() && n) pos = (indices[q] >> shift) & (n - 1);
+        if (ph < proof.log_arities.size()) shift += proof.log_arities[ph];
+        std::vector<uint32_t> r;
+        for (size_t j = 0; j < n; ++j)
+          if (j != pos) r.insert(r.end(), o.row.begin() + j * dc, o.row.begin() + (j + 1) * dc);
+        rows.push_back(std::move(r));
+      }
+    }
+    size_t k = 0;
+    for (const auto& q : proof.query_openings)
+      for (const auto& o : q) {
+        openings.push_back({rows[k].data(), rows[k].size(), o.salts.data(), o.salts.size(), o.siblings.data(), o.siblings.size()});
+        ++k;
+      }
+    view.log_max_height = proof.log_max_height;
+    view.query_pow = proof.query_pow_witness;
+    view.commit_caps = caps.data(); view.commit_caps_len = caps.size();
+    view.commit_pow = proof.commit_pow_witnesses.data(); view.commit_pow_len = proof.commit_pow_witnesses.size();
+    view.log_arities = arities.data(); view.log_arities_len = arities.size();
+    view.final_poly = proof.final_poly.data(); view.final_poly_len = proof.final_poly.size();
+    view.openings = openings.data(); view.openings_len = openings.size();
+    view.n_queries = proof.query_openings.size();
+  }
+};
+}  // namespace detail
+
+struct FriTranscript {
+  std::vector<uint32_t> betas;     // n_phases x DC
+  std::vector<uint32_t> indices;   // n_queries
+};
+// The transcript of verify_fri up to the query indices (p3r_fri_verify_transcript): `challenger` is left where prove_fri
+// left the prover's.  Throws Error: P3R_EVERIFY for a rejected proof, P3R_EINVAL for a malformed one.
+inline FriTranscript verify_fri_transcript(const p3r_config& cfg, HostChallenger& challenger, const FriProof& proof) {
+  const size_t dc = cfg.challenge_degree == 5 ? 5 : 4;
+  const detail::FriProofView v(proof, dc, {});
+  FriTranscript t;
+  t.betas.resize(proof.log_arities.size() * dc + 1);
+  t.indices.resize(proof.query_openings.size() + 1);
+  const int rc = p3r_fri_verify_transcript(&cfg, challenger.raw(), &v.view, t.betas.data(), t.indices.data());
+  if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
+  t.betas.resize(proof.log_arities.size() * dc);
+  t.indices.resize(proof.query_openings.size());
+  return t;
+}
+// p3_fri::verifier::verify_fri (p3r_fri_verify).  `challenger`: the transcript BEFORE the proof; `inputs`: one per input
+// height, tallest first, at the indices verify_fri_transcript gives on a clone.  Accepted: returns, the challenger where the
+// prover's is.  Throws Error: P3R_EVERIFY with the rule and the place, P3R_EINVAL for a malformed proof.
+inline void verify_fri(const p3r_config& cfg, HostChallenger& challenger, const FriProof& proof, const std::vector<FriInput>& inputs) {
+  const size_t dc = cfg.challenge_degree == 5 ? 5 : 4;
+  HostChallenger probe(challenger);
+  const FriTranscript t = verify_fri_transcript(cfg, probe, proof);   // the queried element of every row: the verifier's own replay
+  const detail::FriProofView v(proof, dc, t.indices);
+  std::vector<p3r_fri_input_view> ins;
+  for (const FriInput& in : inputs) ins.push_back({in.log_height, in.values.data(), in.values.size()});
+  const int rc = p3r_fri_verify(&cfg, challenger.raw(), &v.view, ins.data(), ins.size());
+  if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
+}
+
+// VerifierConstraintFolder for an AirProgram (p3r_air_program_eval): the program at the out-of-domain point zeta from the
+// opened values `local` / `next` (sum(widths) x DC words, at zeta and zeta * w_h).  first: the Horner fold of the
+// constraints with alpha; second: 1 / (zeta^h - 1).
+struct AirEvaluation {
+  std::vector<uint32_t> folded, inv_zh;
+};
+inline AirEvaluation eval_at(const AirProgram& program, const p3r_config& cfg, const std::vector<size_t>& widths,
+                             const std::vector<uint32_t>& local, const std::vector<uint32_t>& next, uint32_t log_height,
+                             const std::vector<uint32_t>& zeta, const std::vector<uint32_t>& alpha,
+                             const std::vector<uint32_t>& public_values = {}, const std::vector<uint32_t>& challenges = {}) {
+  const size_t dc = cfg.challenge_degree == 5 ? 5 : 4;
+  size_t total = 0;
+  for (size_t w : widths) total += w;
+  if (zeta.size() != dc || alpha.size() != dc || challenges.size() % dc || local.size() != total * dc || next.size() != total * dc)
+    throw Error(P3R_EINVAL, "eval_at: zeta and alpha are DC words, challenges DC words each, the opened values sum(widths) x DC");
+  AirEvaluation out{std::vector<uint32_t>(dc), std::vector<uint32_t>(dc)};
+  const int rc = p3r_air_program_eval(&cfg, program.insns().data(), program.insns().size(), widths.data(), widths.size(), local.data(),
+                                      next.data(), log_height, zeta.data(), public_values.data(), public_values.size(), challenges.data(),
+                                      challenges.size() / dc, alpha.data(), out.folded.data(), out.inv_zh.data());
+  if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
+  return out;
+}
+
+inline AirProgram::Evaluation AirProgram::eval_at(const p3r_config& cfg, const std::vector<size_t>& widths, const std::vector<uint32_t>& local,
+                                                  const std::vector<uint32_t>& next, uint32_t log_height, const std::vector<uint32_t>& zeta,
+                                                  const std::vector<uint32_t>& alpha, const std::vector<uint32_t>& public_values,
+                                                  const std::vector<uint32_t>& challenges) const {
+  AirEvaluation e = p3r::eval_at(*this, cfg, widths, local, next, log_height, zeta, alpha, public_values, challenges);
+  return Evaluation{std::move(e.folded), std::move(e.inv_zh)};
 }
 
 }  // namespace p3r

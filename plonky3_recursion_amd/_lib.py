@@ -24,6 +24,7 @@ P3R_EXT_ZK_DETERMINISTIC = 4        # ZK key taken as it is, p3r_zk_set_nonce al
 P3R_AIR_LOOKUP, P3R_AIR_LOOKUP_END = 21, 22
 P3R_AIR_MAX_LIVE = 48
 P3R_LOOKUP_CHECK_MAX_RECORDS = 1 << 28    # p3r_lookup_check_dmat: term slots (rows x terms over the instances) of one call
+P3R_EINVAL, P3R_EUNSUPPORTED, P3R_EVERIFY = -1, -5, -7   # P3R_EVERIFY: a well-formed proof the FRI verifier seam rejects
 FIELD_KOALA_BEAR = 0
 FIELD_BABY_BEAR = 1
 
@@ -111,6 +112,25 @@ class P3rLookupInstance(C.Structure):   # p3r_lookup_check_dmat: one table on th
 class P3rLookupImbalance(C.Structure):   # p3r_lookup_check_dmat: one unbalanced key
     _fields_ = [("instance", C.c_uint32), ("row", C.c_uint32), ("term", C.c_uint32), ("n_records", C.c_uint32),
                 ("denominator", C.c_uint32 * 5), ("net", C.c_uint32 * 5)]
+
+
+class P3rFriPhaseOpeningView(C.Structure):   # p3r_fri_verify: one commit-phase opening of one query
+    _fields_ = [("row", C.POINTER(C.c_uint32)), ("row_len", C.c_size_t), ("salts", C.POINTER(C.c_uint32)), ("salts_len", C.c_size_t),
+                ("siblings", C.POINTER(C.c_uint32)), ("siblings_len", C.c_size_t)]
+
+
+class P3rFriProofView(C.Structure):   # p3r_fri_verify: what prove_fri returns, every array a pointer and a length in words
+    _fields_ = [("log_max_height", C.c_uint32), ("query_pow", C.c_uint32),
+                ("commit_caps", C.POINTER(C.c_uint32)), ("commit_caps_len", C.c_size_t),
+                ("commit_pow", C.POINTER(C.c_uint32)), ("commit_pow_len", C.c_size_t),
+                ("log_arities", C.POINTER(C.c_uint8)), ("log_arities_len", C.c_size_t),
+                ("final_poly", C.POINTER(C.c_uint32)), ("final_poly_len", C.c_size_t),
+                ("openings", C.POINTER(P3rFriPhaseOpeningView)), ("openings_len", C.c_size_t),
+                ("n_queries", C.c_size_t)]
+
+
+class P3rFriInputView(C.Structure):   # p3r_fri_verify: the reduced openings of one input height at the query indices
+    _fields_ = [("log_height", C.c_uint32), ("values", C.POINTER(C.c_uint32)), ("values_len", C.c_size_t)]
 
 
 class P3rAirDesc(C.Structure):
@@ -256,6 +276,12 @@ SIGNATURES = {
     "p3r_fri_leaf_view_dmat": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(vp)]),
     "p3r_fri_final_poly_dmat": (C.c_int, [vp, vp, C.c_uint32, u32p]),
     "p3r_fri_log_arity": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "p3r_air_program_eval": (C.c_int, [C.POINTER(P3rConfig), C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t, u32p, u32p,
+                                       C.c_uint32, u32p, u32p, C.c_size_t, u32p, C.c_size_t, u32p, u32p, u32p]),
+    "p3r_challenger_create_host": (vp, [C.POINTER(P3rConfig)]),
+    "p3r_fri_log_arity_cfg": (C.c_int, [C.POINTER(P3rConfig), C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "p3r_fri_verify_transcript": (C.c_int, [C.POINTER(P3rConfig), vp, C.POINTER(P3rFriProofView), u32p, u32p]),
+    "p3r_fri_verify": (C.c_int, [C.POINTER(P3rConfig), vp, C.POINTER(P3rFriProofView), C.POINTER(P3rFriInputView), C.c_size_t]),
     # the caller's AIR as a constraint program (quotient_values + split_evals on resident LDEs)
     "p3r_air_program_info": (C.c_int, [C.POINTER(P3rConfig), C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
                                        C.POINTER(P3rAirInfo)]),

@@ -7,88 +7,12 @@
 #include <algorithm>
 #include <chrono>
 
-#include "poseidon2_rc_default.inc"
-#include "poseidon2_w32_default.inc"
 #include "verify_impl.h"
+#include "fri_verify_abi.h"
 
 using namespace p3r;
 
 namespace {
-
-// The permutation constants of a configuration, canonical: the width-16 round constants, then the width-32 table
-// (round constants | diagonal, poseidon2.h) - the layout of p3r_ctx::rc and of the verifier's table.  NULL pointers
-// select the self-generated defaults.  `bad`: reports a length mismatch.
-template <class PP, class Bad>
-std::vector<uint32_t> constants_table(const p3r_config& cfg, Bad&& bad) {
-  const size_t nrc = p2_num_constants<PP>(), nrcw = p2w_num_rc<PP>();
-  const uint32_t* src = cfg.poseidon2_rc;
-  if (src && cfg.poseidon2_rc_len != nrc) bad("poseidon2_rc_len", cfg.poseidon2_rc_len, nrc);
-  if (!src) src = PP::FIELD_ID == 0 ? kDefaultRc_koala_bear : kDefaultRc_baby_bear;
-  const uint32_t* w = cfg.poseidon2_w32_rc;
-  if (w && cfg.poseidon2_w32_rc_len != nrcw) bad("poseidon2_w32_rc_len", cfg.poseidon2_w32_rc_len, nrcw);
-  if (!w) w = PP::FIELD_ID == 0 ? kDefaultRcW32_koala_bear : kDefaultRcW32_baby_bear;
-  const uint32_t* dg = cfg.poseidon2_w32_diag ? cfg.poseidon2_w32_diag : (PP::FIELD_ID == 0 ? kDefaultDiagW32_koala_bear : kDefaultDiagW32_baby_bear);
-  std::vector<uint32_t> t(src, src + nrc);
-  t.insert(t.end(), w, w + nrcw);
-  t.insert(t.end(), dg, dg + P2W_WIDTH);
-  for (size_t i = 0; i < t.size(); ++i)
-    if (t[i] >= PP::P) p3r::vfail("%s constant %zu is not canonical (%u >= p)", i < nrc ? "poseidon2_rc" : "width-32 permutation", i < nrc ? i : i - nrc, t[i]);
-  return t;
-}
-
-// p3r.h: P3R_EXT_UNPINNED_W32_DEFAULTS
-inline bool w32_unacknowledged(const p3r_config& cfg) {
-  return (!cfg.poseidon2_w32_rc || !cfg.poseidon2_w32_diag) && !(cfg.ext_choices & P3R_EXT_UNPINNED_W32_DEFAULTS);
-}
-constexpr const char* kW32Unpinned =
-    "the width-32 permutation with poseidon2_w32_rc / poseidon2_w32_diag NULL: the built-in constants are self-generated, not "
-    "upstream's - pass the caller's, or acknowledge with P3R_EXT_UNPINNED_W32_DEFAULTS";
-
-template <class PP>
-std::vector<uint32_t> host_constants_table(const p3r_config& cfg) {
-  return constants_table<PP>(cfg, [](const char* what, uint32_t got, size_t want) {
-    p3r::vfail("%s is %u, the field needs %zu constants", what, got, want);
-  });
-}
-
-// ---- the frame of every entry point below: a refusal is a code and a text; anything thrown is P3R_EINVAL with its text
-struct Refused { int code; const char* text; };
-[[noreturn]] inline void refuse(int code, const char* text) { throw Refused{code, text}; }
-template <class Body>
-int guarded(char* err_buf, size_t err_cap, Body&& body) {
-  auto report = [&](const char* msg) {
-    if (err_buf && err_cap) snprintf(err_buf, err_cap, "%s", msg);
-  };
-  try {
-    return body();
-  } catch (const Refused& r) {
-    report(r.text);
-    return r.code;
-  } catch (const std::exception& e) {
-    report(e.what());
-    return P3R_EINVAL;
-  }
-}
-template <class Run>
-void for_field(uint32_t field, Run&& run) {
-  if (field == P3R_FIELD_KOALA_BEAR) run(p3r::KoalaBearParams{});
-  else if (field == P3R_FIELD_BABY_BEAR) run(p3r::BabyBearParams{});
-  else refuse(P3R_EINVAL, "unknown field");
-}
-
-// what p3r_mmcs_verify and p3r_verify_batch ask of a configuration's MMCS.  `uses_w32`: something of the call runs over
-// the width-32 permutation (the arity-4 MMCS does; so does its AIR's table)
-inline void check_mmcs_config(const p3r_config& cfg, bool uses_w32) {
-  if (cfg.mmcs_arity != 0 && cfg.mmcs_arity != 2 && cfg.mmcs_arity != 4) refuse(P3R_EINVAL, "mmcs_arity must be 2 or 4");
-  if (cfg.mmcs_arity == 4 && cfg.cap_height != 0) refuse(P3R_EUNSUPPORTED, "arity-4 MMCS: cap_height must be 0");
-  if ((uses_w32 || cfg.mmcs_arity == 4) && w32_unacknowledged(cfg)) refuse(P3R_EINVAL, kW32Unpinned);
-}
-inline void check_salt_elems(const p3r_config& cfg) {
-  if (cfg.mmcs_salt_elems > 16) refuse(P3R_EINVAL, "mmcs_salt_elems must be in 0..16");
-}
-inline void check_width(size_t w) {
-  if (w > (size_t(1) << 24)) refuse(P3R_EINVAL, "matrix width out of range");
-}
 
 struct ProofFlags {
   bool canonical, zk, salted, quintic;

@@ -6,6 +6,7 @@
 #include "kernels_coop.hip.h"
 #include "tu_api.h"
 #include "air_program.h"
+#include "air_program_eval.h"
 #include "profile.h"
 #include "run_schedule.h"
 #include "prep_device.h"
@@ -22,8 +23,6 @@
 using namespace p3r;
 
 namespace {
-
-thread_local std::string g_create_error;
 
 template <class Fn>
 int guard(p3r_ctx* ctx, Fn&& fn) {
@@ -298,41 +297,6 @@ void fri_final_poly_canonical(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t lf, ui
     else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
   }
   fri_final_poly_dc<PP, 4>(ctx, vec, lf, coeffs_out);
-}
-}  // namespace
-
-// p3r_challenger: a thin handle around HostChallenger<PP, DC> (host_transcript.h), DC the context's challenge degree
-struct p3r_challenger {
-  p3r_ctx* ctx = nullptr;
-  int tag = 0;                // 0: KoalaBear, DC = 4; 1: KoalaBear, DC = 5; 2: BabyBear, DC = 4
-  std::vector<uint32_t> rc;   // the context's width-16 constants, Montgomery: what the HostChallenger points at
-  std::shared_ptr<void> impl;
-};
-namespace {
-template <class Fn>
-void challenger_visit(const p3r_challenger* ch, Fn&& fn) {
-  switch (ch->tag) {
-    case 0: fn(*static_cast<HostChallenger<KoalaBearParams, 4>*>(ch->impl.get())); break;
-    case 1: fn(*static_cast<HostChallenger<KoalaBearParams, 5>*>(ch->impl.get())); break;
-    default: fn(*static_cast<HostChallenger<BabyBearParams, 4>*>(ch->impl.get())); break;
-  }
-}
-// a fresh transcript, or a copy of src's (same tag), over ch's own copy of the constants
-inline void challenger_make(p3r_challenger* ch, const p3r_challenger* src) {
-  auto make = [&](auto tag) {
-    using C = decltype(tag);
-    auto c = std::make_shared<C>(ch->rc.data());
-    if (src) {
-      *c = *static_cast<const C*>(src->impl.get());
-      c->rc = ch->rc.data();
-    }
-    ch->impl = c;
-  };
-  switch (ch->tag) {
-    case 0: make(HostChallenger<KoalaBearParams, 4>(nullptr)); break;
-    case 1: make(HostChallenger<KoalaBearParams, 5>(nullptr)); break;
-    default: make(HostChallenger<BabyBearParams, 4>(nullptr)); break;
-  }
 }
 }  // namespace
 
@@ -813,6 +777,7 @@ int p3r_challenger_check_witness(p3r_challenger* ch, uint32_t bits, uint32_t wit
 }
 int p3r_challenger_grind(p3r_ctx* ctx, p3r_challenger* ch, uint32_t bits, uint32_t* witness_out) {
   return guard(ctx, [&] {
+    if (ch && !ch->ctx) fail(P3R_EINVAL, "a host challenger (p3r_challenger_create_host) cannot grind: the search runs on a device");
     if (!ctx || !ch) fail(P3R_EINVAL, "ctx or challenger is NULL");
     if (!witness_out) fail(P3R_EINVAL, "witness_out is NULL");
     if (ch->ctx != ctx) fail(P3R_EINVAL, "the challenger belongs to another context");
@@ -852,6 +817,30 @@ int p3r_air_program_info(const p3r_config* cfg, const p3r_air_insn* prog, size_t
     const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
     *out = air_plan(prog, n_insns, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p, kAirUnknownCount, kAirUnknownCount,
                     P3R_AIR_MAX_LIVE).info;
+  });
+}
+// The verifier's side of a constraint program: air_program_eval.h (host only)
+int p3r_air_program_eval(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
+                         const uint32_t* local, const uint32_t* next, uint32_t log_height, const uint32_t* zeta, const uint32_t* public_values,
+                         size_t n_public, const uint32_t* challenges, size_t n_challenges, const uint32_t* alpha, uint32_t* folded_out,
+                         uint32_t* inv_zh_out) {
+  return guard(nullptr, [&] {
+    if (!cfg) fail(P3R_EINVAL, "cfg is NULL");
+    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
+    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
+      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
+    if (cfg->zk) fail(P3R_EUNSUPPORTED, "zk configurations: their doubled domains are out of scope of the program seams");
+    if (cfg->field == P3R_FIELD_BABY_BEAR) {
+      if (cfg->challenge_degree == 5) fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+      air_program_eval<BabyBearParams, 4>(prog, n_insns, widths, n_mats, local, next, log_height, zeta, public_values, n_public, challenges,
+                                          n_challenges, alpha, folded_out, inv_zh_out);
+    } else if (cfg->challenge_degree == 5) {
+      air_program_eval<KoalaBearParams, 5>(prog, n_insns, widths, n_mats, local, next, log_height, zeta, public_values, n_public, challenges,
+                                           n_challenges, alpha, folded_out, inv_zh_out);
+    } else {
+      air_program_eval<KoalaBearParams, 4>(prog, n_insns, widths, n_mats, local, next, log_height, zeta, public_values, n_public, challenges,
+                                           n_challenges, alpha, folded_out, inv_zh_out);
+    }
   });
 }
 int p3r_quotient_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,

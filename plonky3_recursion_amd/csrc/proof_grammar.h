@@ -19,18 +19,6 @@
 
 namespace p3r {
 
-struct VerifyFailure : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-[[noreturn]] inline void vfail(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  throw VerifyFailure(buf);
-}
-
 // ---- postcard reader (mirror of ProofWriter)
 struct PostcardCursor {
   const uint8_t* p;

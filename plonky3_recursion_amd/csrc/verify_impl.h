@@ -21,6 +21,7 @@
 #include <string>
 
 #include "../../include/p3r.h"
+#include "fri_verify.h"
 #include "proof_grammar.h"
 
 namespace p3r {
@@ -196,137 +197,6 @@ struct ZetaLookupSink {
   }
 };
 
-// ---- MMCS
-// a digest is the first P2_DIGEST words of the permutation state, at either width
-template <class F>
-std::array<F, P2_DIGEST> state_digest(const F* s) {
-  std::array<F, P2_DIGEST> d;
-  std::copy(s, s + P2_DIGEST, d.begin());
-  return d;
-}
-template <class PP>
-std::array<Fp<PP>, P2_DIGEST> sponge_hash(const std::vector<Fp<PP>>& row, const uint32_t* rc) {
-  using F = Fp<PP>;
-  F s[P2_WIDTH];
-  for (auto& x : s) x = F::zero();
-  size_t g = 0;
-  // overwrite-mode PaddingFreeSponge, rate 8 (recursion/src/pcs/mmcs.rs:38-179)
-  for (; g < row.size(); g += P2_RATE) {
-    for (size_t j = 0; j < (size_t)P2_RATE && g + j < row.size(); ++j) s[j] = row[g + j];
-    host_permute<PP>(s, rc);
-  }
-  return state_digest(s);
-}
-template <class PP>
-std::array<Fp<PP>, P2_DIGEST> compress2(const std::array<Fp<PP>, P2_DIGEST>& l, const std::array<Fp<PP>, P2_DIGEST>& r,
-                                        const uint32_t* rc) {
-  Fp<PP> s[P2_WIDTH];
-  for (int k = 0; k < P2_DIGEST; ++k) { s[k] = l[k]; s[P2_DIGEST + k] = r[k]; }
-  host_permute<PP>(s, rc);
-  return state_digest(s);
-}
-
-// verify_batch of one commitment: `log_heights[m]` / rows[m] in COMMIT order; index addresses the
-// tallest matrix.  (recursion/src/pcs/mmcs.rs:319-426)
-template <class PP>
-void mmcs_verify(const std::vector<std::array<Fp<PP>, P2_DIGEST>>& cap, int cap_height, const std::vector<int>& log_heights,
-                 const std::vector<std::vector<Fp<PP>>>& rows, size_t index,
-                 const std::vector<std::array<Fp<PP>, P2_DIGEST>>& path, const uint32_t* rc, const char* what) {
-  using F = Fp<PP>;
-  if (rows.size() != log_heights.size()) vfail("%s: %zu opened rows for %zu matrices", what, rows.size(), log_heights.size());
-  int log_max = 0;
-  for (int lh : log_heights) log_max = std::max(log_max, lh);
-  if (cap_height > log_max || cap.size() != (size_t(1) << cap_height)) vfail("%s: bad cap", what);
-  if ((int)path.size() != log_max - cap_height) vfail("%s: opening proof has %zu siblings, expected %d", what, path.size(), log_max - cap_height);
-  if (index >> log_max) vfail("%s: index out of range", what);
-  auto concat = [&](int lh) {
-    std::vector<F> r;
-    for (size_t m = 0; m < rows.size(); ++m)
-      if (log_heights[m] == lh) r.insert(r.end(), rows[m].begin(), rows[m].end());
-    return r;
-  };
-  auto any_at = [&](int lh) {
-    for (int x : log_heights) if (x == lh) return true;
-    return false;
-  };
-  auto node = sponge_hash<PP>(concat(log_max), rc);
-  size_t idx = index;
-  for (int lvl = 0; lvl < log_max - cap_height; ++lvl) {
-    node = (idx & 1) ? compress2<PP>(path[lvl], node, rc) : compress2<PP>(node, path[lvl], rc);
-    idx >>= 1;
-    const int lh = log_max - lvl - 1;
-    if (any_at(lh)) node = compress2<PP>(node, sponge_hash<PP>(concat(lh), rc), rc);  // injection
-  }
-  if (node != cap.at(idx)) vfail("%s: Merkle root mismatch", what);
-}
-
-// Arity-4 MMCS (mmcs4.h): leaf = width-32 sponge of rate 24 over the rows of the tallest matrices; per level step - 1
-// siblings in ascending position around the running digest at `pos = index mod step`, chunks above `step` zero; an
-// injected class as one more compression (node, digest of its rows, 0, 0).  recursion/src/pcs/mmcs.rs:1165-1316 is
-// the same walk in circuit form.  `rcw`: the width-32 constant table (Montgomery), rc + p2_num_constants.
-template <class PP>
-std::array<Fp<PP>, P2_DIGEST> sponge_hash_w32(const std::vector<Fp<PP>>& row, const uint32_t* rcw) {
-  using F = Fp<PP>;
-  F s[P2W_WIDTH];
-  for (auto& x : s) x = F::zero();
-  struct { void put(F) {} } sink;
-  for (size_t g = 0; g < row.size(); g += 24) {
-    for (size_t j = 0; j < 24 && g + j < row.size(); ++j) s[j] = row[g + j];
-    p2w_permute_traced<PP>(s, rcw, sink);
-  }
-  return state_digest(s);
-}
-template <class PP>
-std::array<Fp<PP>, P2_DIGEST> compress4(const std::array<Fp<PP>, P2_DIGEST>* c, const uint32_t* rcw) {
-  using F = Fp<PP>;
-  F s[P2W_WIDTH];
-  for (int j = 0; j < 4; ++j)
-    for (int k = 0; k < P2_DIGEST; ++k) s[j * P2_DIGEST + k] = c[j][k];
-  struct { void put(F) {} } sink;
-  p2w_permute_traced<PP>(s, rcw, sink);
-  return state_digest(s);
-}
-template <class PP>
-void mmcs_verify4(const std::vector<std::array<Fp<PP>, P2_DIGEST>>& cap, int cap_height, const std::vector<int>& log_heights,
-                  const std::vector<std::vector<Fp<PP>>>& rows, size_t index,
-                  const std::vector<std::array<Fp<PP>, P2_DIGEST>>& path, const uint32_t* rcw, const char* what) {
-  using F = Fp<PP>;
-  using Digest = std::array<F, P2_DIGEST>;
-  if (rows.size() != log_heights.size() || rows.empty()) vfail("%s: %zu opened rows for %zu matrices", what, rows.size(), log_heights.size());
-  if (cap_height != 0 || cap.size() != 1) vfail("%s: bad cap (the arity-4 MMCS has a one-digest cap)", what);
-  int log_max = 0;
-  std::vector<size_t> heights;
-  for (int lh : log_heights) {
-    log_max = std::max(log_max, lh);
-    heights.push_back(size_t(1) << lh);
-  }
-  if (index >> log_max) vfail("%s: index out of range", what);
-  const std::vector<MmcsLevel> levels = mmcs4_schedule(heights);
-  if (path.size() != mmcs_proof_len(levels))
-    vfail("%s: opening proof has %zu siblings, expected %zu", what, path.size(), mmcs_proof_len(levels));
-  auto concat = [&](size_t h) {
-    std::vector<F> r;
-    for (size_t m = 0; m < rows.size(); ++m)
-      if (heights[m] == h) r.insert(r.end(), rows[m].begin(), rows[m].end());
-    return r;
-  };
-  Digest zero;
-  zero.fill(F::zero());
-  Digest node = sponge_hash_w32<PP>(concat(size_t(1) << log_max), rcw);
-  size_t at = 0;
-  for (const MmcsLevel& lv : levels) {
-    const size_t pos = (index >> lv.bits) & (size_t)(lv.step - 1);
-    Digest c[4] = {zero, zero, zero, zero};
-    for (size_t j = 0; j < (size_t)lv.step; ++j) c[j] = j == pos ? node : path[at++];
-    node = compress4<PP>(c, rcw);
-    if (lv.inject_h) {
-      Digest in[4] = {node, sponge_hash_w32<PP>(concat(lv.inject_h), rcw), zero, zero};
-      node = compress4<PP>(in, rcw);
-    }
-  }
-  if (node != cap[0]) vfail("%s: Merkle root mismatch", what);
-}
-
 // ---- the out-of-domain identity of one instance: folded constraints(zeta) / Z_H(zeta) == quotient(zeta)
 // (recursion/src/verifier/batch_stark.rs:886-1017, verifier/quotient.rs:60-140).  Shared by the
 // verifier and by the prover's self-check before it serialises a proof (prove_impl.hip.h): the
@@ -444,51 +314,6 @@ struct VerifyParams {
   int mmcs_salt_elems = 0;               // MerkleTreeHidingMmcs: salt elements per committed row (p3r_config.mmcs_salt_elems)
 };
 
-// MerkleTreeHidingMmcs::verify_batch through the plain walk: the leaf preimage of a height class is the concatenation of
-// [row | salt] per matrix (recursion/src/pcs/mmcs.rs:375-389 for base rows, :470-486 for flattened extension rows), i.e.
-// the plain preimage of the matrices widened by their salts.
-template <class F>
-std::vector<std::vector<F>> salted_rows(const std::vector<std::vector<F>>& rows, const std::vector<std::vector<F>>& salts, int salt_elems,
-                                        const char* what) {
-  if (!salt_elems) {
-    if (!salts.empty()) vfail("%s: salts under a non-hiding MMCS", what);
-    return rows;
-  }
-  if (salts.size() != rows.size()) vfail("%s: %zu salts for %zu matrices", what, salts.size(), rows.size());
-  std::vector<std::vector<F>> out(rows);
-  for (size_t m = 0; m < rows.size(); ++m) {
-    if ((int)salts[m].size() != salt_elems) vfail("%s: a salt of %zu elements, expected %d", what, salts[m].size(), salt_elems);
-    out[m].insert(out[m].end(), salts[m].begin(), salts[m].end());
-  }
-  return out;
-}
-
-// One MMCS as a verifier sees it.  `rc`: the permutation constants in Montgomery form, the width-16 round constants
-// followed by the width-32 table (poseidon2.h; csrc/p3r_core.hip::constants_table).
-template <class PP>
-struct MmcsChecker {
-  using F = Fp<PP>;
-  using Digest = std::array<F, P2_DIGEST>;
-  int arity, salt_elems;
-  const uint32_t* rc;
-  // Mmcs::verify_batch of one opening: salt the rows, then the walk of the configured arity over its own constants
-  void check_opening(const std::vector<Digest>& cap, int cap_height, const std::vector<int>& log_heights,
-                     const std::vector<std::vector<F>>& rows, const std::vector<std::vector<F>>& salts, size_t index,
-                     const std::vector<Digest>& path, const char* what) const {
-    const auto leaf_rows = salted_rows<F>(rows, salts, salt_elems, what);
-    if (arity == 4) mmcs_verify4<PP>(cap, cap_height, log_heights, leaf_rows, index, path, rc + p2_num_constants<PP>(), what);
-    else mmcs_verify<PP>(cap, cap_height, log_heights, leaf_rows, index, path, rc, what);
-  }
-};
-
-template <class PP>
-std::vector<uint32_t> montgomery_constants(const std::vector<uint32_t>& rc_canonical) {
-  if (rc_canonical.size() != (size_t)p2_num_constants<PP>() + (size_t)p2w_num_constants<PP>()) vfail("wrong number of permutation constants");
-  std::vector<uint32_t> rc(rc_canonical.size());
-  for (size_t i = 0; i < rc.size(); ++i) rc[i] = Fp<PP>::from_canonical(rc_canonical[i]).v;
-  return rc;
-}
-
 // The verifier's state and its phases, named after prove_batch's (prove_impl.hip.h): the members are what crosses a
 // phase boundary, everything else is a local of its phase.
 template <class PP, int DC = 4>
@@ -514,15 +339,19 @@ struct BatchVerifier {
   E alpha, zeta, l_prefix = E::zero(), l_beta_pow[kMaxExtD + 1];
   std::vector<std::vector<Mat>> rounds;
   std::vector<const std::vector<Digest>*> round_caps;
-  std::vector<int> las;
-  std::vector<E> betas, fa_pow;
+  const FriVerifyParams fri_prm;
+  FriVerifier<PP, DC> fri;
+  std::vector<E> fa_pow;
   int log_max = 0;
 
   BatchVerifier(const VerifyParams& prm_, const std::vector<uint32_t>& rc_canonical, const std::vector<AirParams>& airs_,
                 const std::vector<uint32_t>& prep_cap_canonical, const uint8_t* bytes, size_t n_bytes, bool canonical)
       : prm(prm_), airs(airs_), ni(airs_.size()), zk(prm_.zk ? 1 : 0), R(zk ? prm_.num_random_codewords : 0), lb(prm_.log_blowup),
         cap_h(prm_.cap_height), P(parse(prm_, bytes, n_bytes, canonical)), rc(montgomery_constants<PP>(rc_canonical)),
-        mmcs{prm_.mmcs_arity, prm_.mmcs_salt_elems, rc.data()}, prep_cap(size_t(1) << cap_h), ch(rc.data()) {
+        mmcs{prm_.mmcs_arity, prm_.mmcs_salt_elems, rc.data()}, prep_cap(size_t(1) << cap_h), ch(rc.data()),
+        fri_prm{prm_.log_blowup, prm_.max_log_arity, prm_.cap_height, prm_.log_final_poly_len, prm_.commit_pow_bits, prm_.query_pow_bits,
+                prm_.num_queries, &prm_.fri_log_arities},
+        fri(fri_prm, mmcs) {
     if (P.insts.size() != ni || P.degree_bits.size() != ni || P.terminals.size() != ni)
       vfail("proof has %zu instances, the verifier was given %zu AIRs", P.insts.size(), ni);
     if (prep_cap_canonical.size() != prep_cap.size() * P2_DIGEST) vfail("preprocessed commitment has the wrong size");
@@ -670,47 +499,28 @@ struct BatchVerifier {
     if (any_lookup() && !terminal_sum.is_zero()) vfail("global lookup sum is not zero");
   }
 
-  // the FRI transcript: the arity schedule the prover must have used (the FRI prover's rule, prove_impl.hip.h step 7),
-  // the commit caps with their proofs of work and betas, the final polynomial, the query proof of work
+  // the FRI transcript (fri_verify.h): the arity schedule the prover must have used, the commit caps with their proofs
+  // of work and betas, the final polynomial, the query proof of work
   void fri_commit_phase() {
     const E fri_alpha = ch.sample_ext();
     size_t max_w = 1;
     std::vector<int> heights;
-    for (auto& r : rounds) for (auto& m : r) { log_max = std::max(log_max, m.log_h); heights.push_back(m.log_h); max_w = std::max(max_w, (size_t)m.w); }
+    for (auto& r : rounds) for (auto& m : r) { heights.push_back(m.log_h); max_w = std::max(max_w, (size_t)m.w); }
     fa_pow.assign(max_w + 1, E::one());
     for (size_t c = 1; c <= max_w; ++c) fa_pow[c] = fa_pow[c - 1] * fri_alpha;
-    std::sort(heights.rbegin(), heights.rend());
-    heights.erase(std::unique(heights.begin(), heights.end()), heights.end());
-    const int log_final = prm.log_final_poly_len + lb;
-    size_t next_h = 1;
-    int cur = log_max;
-    while (cur > log_final) {
-      int log_next = next_h < heights.size() ? heights[next_h] : -1;
-      const int la = fri_log_arity(prm.fri_log_arities, las.size(), prm.max_log_arity, cur, log_final, log_next);
-      if (la < 0) vfail("FRI: the configured folding schedule does not fit the proof (phase %zu)", las.size());
-      if (next_h < heights.size() && heights[next_h] == cur - la) ++next_h;
-      cur -= la;
-      las.push_back(la);
-    }
-    if (next_h != heights.size()) vfail("FRI: an input height is never rolled in");
-    if (cur != log_final) vfail("FRI: fold schedule does not end at the final polynomial length");
-    if (P.commit_caps.size() != las.size() || P.commit_pow.size() != las.size()) vfail("FRI: %zu commit phases, expected %zu", P.commit_caps.size(), las.size());
-    if (P.final_poly.size() != (size_t(1) << prm.log_final_poly_len)) vfail("FRI: final polynomial has the wrong length");
-    for (size_t p = 0; p < las.size(); ++p) {
-      observe_cap(P.commit_caps[p]);
-      if (!ch.check_witness(prm.commit_pow_bits, P.commit_pow[p])) vfail("FRI: invalid commit-phase proof of work");
-      betas.push_back(ch.sample_ext());
-    }
-    for (auto& c : P.final_poly) ch.observe_ext(c);
-    for (int la : las) ch.observe(F::from_canonical((uint32_t)la));
-    if (!ch.check_witness(prm.query_pow_bits, P.query_pow)) vfail("FRI: invalid query proof of work");
-    if ((int)P.queries.size() != prm.num_queries) vfail("FRI: %zu queries, expected %d", P.queries.size(), prm.num_queries);
+    fri.schedule(heights);
+    log_max = fri.log_max;
+    fri.commit_phase(ch, P.commit_caps, P.commit_pow, P.final_poly, P.query_pow, P.queries.size());
   }
 
   void queries() {
     for (size_t qi = 0; qi < P.queries.size(); ++qi) {
       const size_t index = ch.sample_bits(log_max);
-      fold_chain(qi, index, input_openings(qi, index));
+      const Reduced ro = input_openings(qi, index);
+      fri.fold_chain(qi, index, P.queries[qi].phases, P.commit_caps, P.final_poly, [&](int log_h) -> const E* {
+        auto it = ro.find(log_h);
+        return it == ro.end() ? nullptr : &it->second.second;
+      });
     }
   }
 
@@ -749,54 +559,6 @@ struct BatchVerifier {
       }
     }
     return ro;
-  }
-
-  // the fold chain of one query down to the final polynomial (pcs/fri/verifier.rs:562-781)
-  void fold_chain(size_t qi, size_t index, const Reduced& ro) const {
-    const auto& Q = P.queries[qi];
-    if (Q.phases.size() != las.size()) vfail("query %zu: %zu commit-phase openings, expected %zu", qi, Q.phases.size(), las.size());
-    if (!ro.count(log_max)) vfail("query %zu: no reduced opening at the maximum height", qi);
-    E folded = ro.at(log_max).second;
-    size_t idx = index;
-    int cur = log_max;
-    const F neg_half = -(F::from_canonical(2).inv());
-    for (size_t p = 0; p < las.size(); ++p) {
-      const auto& ph = Q.phases[p];
-      const int la = las[p];
-      const size_t arity = size_t(1) << la, pos = idx & (arity - 1), row = idx >> la;
-      if (ph.la != la || ph.sibs.size() != arity - 1) vfail("query %zu phase %zu: wrong arity", qi, p);
-      std::vector<E> e(arity);
-      for (size_t j = 0, s = 0; j < arity; ++j) e[j] = j == pos ? folded : ph.sibs[s++];
-      // the leaf is the row of 2^la sibling evaluations, extension elements flattened
-      std::vector<F> leaf;
-      for (auto& x : e) for (int k = 0; k < DC; ++k) leaf.push_back(x.c[k]);
-      mmcs.check_opening(P.commit_caps[p], cap_h, {cur - la}, {leaf}, ph.salts, row, ph.path, "FRI commit phase");
-      F ss_inv = F::two_adic_generator(cur).inv().pow(bit_reverse((uint32_t)row, cur - la));
-      E b = betas[p];
-      const F omega = F::two_adic_generator(la);
-      size_t len = arity;
-      for (int s = 0; s < la; ++s) {
-        const F om_s = omega.pow(uint64_t(1) << s);
-        for (size_t j = 0; j < len / 2; ++j) {
-          const F x0_inv = ss_inv * om_s.pow(bit_reverse((uint32_t)(2 * j), la - s)).inv();
-          const E t = b * x0_inv - E::one();  // arity2_fold_at_point: e0 + (beta - x0)(e1 - e0)(-1/2)/x0
-          e[j] = e[2 * j] + t * (e[2 * j + 1] - e[2 * j]) * neg_half;
-        }
-        len /= 2;
-        ss_inv = ss_inv.sqr();
-        b = b.sqr();
-      }
-      folded = e[0];
-      cur -= la;
-      idx = row;
-      auto it = ro.find(cur);
-      if (it != ro.end() && cur != log_max) folded += betas[p].pow(arity) * it->second.second;  // roll-in
-    }
-    // final polynomial at x = w^{bitrev(idx)} of the size-2^cur domain (verifier.rs:887-915)
-    const F x = F::two_adic_generator(cur).pow(bit_reverse((uint32_t)idx, cur));
-    E eval = E::zero();
-    for (size_t k = P.final_poly.size(); k-- > 0;) eval = eval * x + P.final_poly[k];
-    if (!(eval == folded)) vfail("query %zu: final polynomial mismatch", qi);
   }
 };
 

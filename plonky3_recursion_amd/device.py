@@ -173,6 +173,239 @@ def mmcs_verify(cfg, cap, dims, index, opened_values, proof, salts=None):
         raise P3rError(rc, err.value.decode())
 
 
+class _HostSide:
+    """What a Challenger needs of its owner when there is no context: the library, the challenge degree and the error
+    text of p3r_last_error(NULL)."""
+    h = None
+
+    def __init__(self, cfg):
+        self.lib, self.cfg, self.challenge_degree = _lib.load(), cfg, 5 if cfg.challenge_degree == 5 else 4
+
+    def check(self, rc):
+        if rc != 0:
+            raise P3rError(rc, self.lib.p3r_last_error(None).decode())
+
+    def ptr(self, p):
+        if not p:
+            raise P3rError(-1, self.lib.p3r_last_error(None).decode())
+        return p
+
+
+def host_challenger(cfg):
+    """A fresh DuplexChallenger made from a p3r_config alone (p3r_challenger_create_host; no GPU): the transcript of
+    Context.challenger() for the same configuration, word for word.  Only `grind` refuses it."""
+    side = _HostSide(cfg)
+    return Challenger(side, side.ptr(side.lib.p3r_challenger_create_host(C.byref(cfg))))
+
+
+def fri_log_arity(cfg, phase, log_cur, log_final, log_next_input=-1):
+    """Context.fri_log_arity from a p3r_config alone (p3r_fri_log_arity_cfg)."""
+    return int(_lib.load().p3r_fri_log_arity_cfg(C.byref(cfg), int(phase), int(log_cur), int(log_final), int(log_next_input)))
+
+
+def _fri_proof_view(cfg, proof, indices):
+    """The p3r_fri_proof_view of a FriProof, and the arrays it points into.  `indices`: the query indices, which say what
+    element of every opened row is the queried one (the view carries the row without it); None: rows are passed whole
+    minus element 0 (the transcript entry does not read them)."""
+    dc = 5 if cfg.challenge_degree == 5 else 4
+    keep = []
+
+    def arr(a, dtype=np.uint32):
+        a = np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(-1))
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(C.c_uint8 if dtype == np.uint8 else C.c_uint32)), a.size
+
+    v = _lib.P3rFriProofView()
+    v.log_max_height, v.query_pow = int(proof.log_max_height), int(proof.query_pow_witness)
+    caps = [np.asarray(c, dtype=np.uint32).reshape(-1) for c in proof.commit_phase_caps]
+    v.commit_caps, v.commit_caps_len = arr(np.concatenate(caps) if caps else [])
+    v.commit_pow, v.commit_pow_len = arr(proof.commit_pow_witnesses)
+    v.log_arities, v.log_arities_len = arr(proof.log_arities, np.uint8)
+    v.final_poly, v.final_poly_len = arr(proof.final_poly if proof.final_poly is not None else [])
+    nq = len(proof.query_openings)
+    flat = [(q, ph, o) for q, openings in enumerate(proof.query_openings) for ph, o in enumerate(openings)]
+    ops = (_lib.P3rFriPhaseOpeningView * max(1, len(flat)))()
+    for k, (q, ph, o) in enumerate(flat):
+        row = np.asarray(o.row, dtype=np.uint32).reshape(-1, dc)
+        pos = 0
+        if indices is not None and ph < len(proof.log_arities):
+            shift = sum(int(a) for a in proof.log_arities[:ph])
+            pos = (int(indices[q]) >> shift) & (row.shape[0] - 1) if row.shape[0] else 0
+        ops[k].row, ops[k].row_len = arr(np.delete(row, pos, axis=0) if row.shape[0] else row)
+        ops[k].salts, ops[k].salts_len = arr(o.salts if o.salts is not None else [])
+        ops[k].siblings, ops[k].siblings_len = arr(o.siblings)
+    keep.append(ops)
+    v.openings, v.openings_len, v.n_queries = ops, len(flat), nq
+    return v, keep
+
+
+def fri_verify_transcript(cfg, ch, proof):
+    """The transcript of verify_fri up to the query indices (p3r_fri_verify_transcript; no GPU): replays the FriProof
+    `proof` on the challenger `ch`, checking both proofs of work.  Returns (betas[(n_phases, DC)], indices) and leaves `ch`
+    where prove_fri left the prover's.  Raises P3rError (P3R_EVERIFY: rejected; P3R_EINVAL: malformed); `ch` then has not
+    moved."""
+    lib = _lib.load()
+    dc = 5 if cfg.challenge_degree == 5 else 4
+    view, keep = _fri_proof_view(cfg, proof, None)
+    betas = np.zeros((max(1, len(proof.log_arities)), dc), dtype=np.uint32)
+    idx = np.zeros(max(1, view.n_queries), dtype=np.uint32)
+    rc = lib.p3r_fri_verify_transcript(C.byref(cfg), ch.h, C.byref(view), betas.ctypes.data_as(_lib.u32p), idx.ctypes.data_as(_lib.u32p))
+    if rc != 0:
+        raise P3rError(rc, lib.p3r_last_error(None).decode())
+    return betas[:len(proof.log_arities)], [int(i) for i in idx[:view.n_queries]]
+
+
+def fri_verify(cfg, ch, proof, inputs):
+    """p3_fri::verifier::verify_fri on the host (p3r_fri_verify; no GPU).  `ch`: the challenger BEFORE the proof; `proof`: a
+    FriProof; `inputs`: (log_height, values[(n_queries, DC)]) per input height, tallest first - values[q] the reduced
+    opening of that height at index_q >> (log_max_height - log_height), the indices being fri_verify_transcript's on a
+    clone of `ch`.  Accepted: returns None and leaves `ch` where the prover's challenger is.  Raises P3rError: P3R_EVERIFY
+    with the rule and the place when the proof is rejected, P3R_EINVAL when it is malformed."""
+    lib = _lib.load()
+    # the queried element of every opened row is left out of the view; which one it is comes from the verifier's own
+    # replay, never from the prover
+    probe = ch.clone()
+    try:
+        _, indices = fri_verify_transcript(cfg, probe, proof)
+    finally:
+        probe.free()
+    view, keep = _fri_proof_view(cfg, proof, indices)
+    ins = (_lib.P3rFriInputView * max(1, len(inputs)))()
+    for k, (log_h, values) in enumerate(inputs):
+        a, p = _u32(np.asarray(values, dtype=np.uint32).reshape(-1))
+        keep.append(a)
+        ins[k].log_height, ins[k].values, ins[k].values_len = int(log_h), p, a.size
+    rc = lib.p3r_fri_verify(C.byref(cfg), ch.h, C.byref(view), ins, len(inputs))
+    if rc != 0:
+        raise P3rError(rc, lib.p3r_last_error(None).decode())
+
+
+class _ChallengeField:
+    """The challenge field on Python integers, for the few elements a verifier's wrapper handles (num_queries rows): the
+    quartic binomial extension x^4 = W (W = 3 / 11) or KoalaBear's quintic trinomial extension x^5 + x^2 - 1."""
+
+    def __init__(self, field, dc):
+        self.p, self.dc, self.w = MODULUS[field], dc, {"koala-bear": 3, "baby-bear": 11}[field]
+        if dc == 5 and field != "koala-bear":
+            raise P3rError(-5, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's")
+
+    def lift(self, x):
+        return [int(x) % self.p] + [0] * (self.dc - 1)
+
+    def add(self, a, b):
+        return [(x + y) % self.p for x, y in zip(a, b)]
+
+    def sub(self, a, b):
+        return [(x - y) % self.p for x, y in zip(a, b)]
+
+    def mul(self, a, b):
+        p, dc = self.p, self.dc
+        t = [0] * (2 * dc - 1)
+        for i, x in enumerate(a):
+            for j, y in enumerate(b):
+                t[i + j] += x * y
+        for k in range(2 * dc - 2, dc - 1, -1):   # x^k, k >= dc, in lower powers
+            c = t[k] % p
+            if dc == 4:
+                t[k - 4] += c * self.w            # x^4 = W
+            else:
+                t[k - 5] += c                     # x^5 = 1 - x^2
+                t[k - 3] -= c
+        return [v % p for v in t[:dc]]
+
+    def pow(self, a, e):
+        r, b = self.lift(1), list(a)
+        while e:
+            if e & 1:
+                r = self.mul(r, b)
+            b = self.mul(b, b)
+            e >>= 1
+        return r
+
+    def inv(self, a):
+        if not any(a):
+            raise P3rError(-1, "division by zero in the challenge field")
+        return self.pow(a, self.p ** self.dc - 2)
+
+
+def _bit_reverse(x, bits):
+    return int(format(x, "0%db" % bits)[::-1], 2) if bits else 0
+
+
+def observe_opened_values(ch, values):
+    """Observes the opened values of a PCS opening on the challenger `ch`: values[round][matrix] is (points, width, DC);
+    rounds, matrices, points and columns in order, DC words per value - what Context.pcs_open observes before it samples
+    alpha, and what the caller of pcs_verify observes for the claimed values."""
+    for rnd in values:
+        for v in rnd:
+            ch.observe(np.asarray(v, dtype=np.uint32).reshape(-1))
+
+
+def pcs_verify(cfg, ch, rounds, fri_proof, input_openings):
+    """TwoAdicFriPcs::verify on the host, composed from public calls (no GPU).  `rounds`: per commitment a tuple
+    (cap, dims, points, values) - the cap, the (LDE height, width) of its matrices in commit order, per matrix its (k, DC)
+    opening points and its claimed (k, width, DC) values.  `fri_proof`: the FriProof; `input_openings`: per round
+    (opened[(n_queries, total_width)], salts[(n_queries, n_mats, S)] or None, siblings[(n_queries, depth, 8)]) - what
+    MerkleTree.open_many gave at index_q >> (log_max_height - the round's tallest height).  `ch`: the challenger after the
+    caller observed the claimed values (observe_opened_values); this call observes nothing itself: it samples alpha,
+    replays the FRI transcript on a clone for the query indices, checks every input opening with mmcs_verify, forms the
+    reduced openings with the formula of p3r_fri_reduce_dmat on Python integers, and calls fri_verify, which leaves `ch`
+    where the prover's challenger is.  Raises P3rError: P3R_EVERIFY with the rule and the place for a rejected opening,
+    P3R_EINVAL for a malformed one."""
+    field = [k for k, v in FIELD_IDS.items() if v == cfg.field][0]
+    dc = 5 if cfg.challenge_degree == 5 else 4
+    E, p, g = _ChallengeField(field, dc), MODULUS[field], GENERATOR[field]
+    if len(input_openings) != len(rounds) or not rounds:
+        raise P3rError(-1, "one input opening per round (%d given, %d rounds)" % (len(input_openings), len(rounds)))
+    alpha = [int(v) for v in ch.sample_ext()]
+    logs = [[int(h).bit_length() - 1 for h, w in dims] for cap, dims, points, values in rounds]
+    log_max = max(max(l) for l in logs)
+    if int(fri_proof.log_max_height) != log_max:
+        raise P3rError(-1, "the FRI proof is over 2^%d rows, the tallest committed matrix has 2^%d" % (fri_proof.log_max_height, log_max))
+    probe = ch.clone()
+    try:
+        _, indices = fri_verify_transcript(cfg, probe, fri_proof)
+    finally:
+        probe.free()
+    max_w = max(int(w) for cap, dims, points, values in rounds for h, w in dims)
+    apow = [E.lift(1)]
+    for _ in range(max_w):
+        apow.append(E.mul(apow[-1], alpha))
+    heights = sorted({l for ls in logs for l in ls}, reverse=True)
+    reduced = {l: [E.lift(0) for _ in indices] for l in heights}
+    for q, index in enumerate(indices):
+        running = {l: E.lift(1) for l in heights}   # one running alpha power per height, restarted per query
+        for r, ((cap, dims, points, values), (opened, salts, siblings)) in enumerate(zip(rounds, input_openings)):
+            opened = np.asarray(opened, dtype=np.uint32)
+            if opened.shape[0] != len(indices) or opened.shape[1] != sum(int(w) for h, w in dims):
+                raise P3rError(-1, "round %d: opened rows must be (n_queries, total width)" % r)
+            try:
+                mmcs_verify(cfg, cap, dims, index >> (log_max - max(logs[r])), opened[q], np.asarray(siblings)[q],
+                            salts=None if salts is None else np.asarray(salts)[q])
+            except P3rError as e:
+                raise P3rError(_lib.P3R_EVERIFY if "mismatch" in str(e) else e.code, "input batch %d of query %d: %s" % (r, q, e)) from None
+            at = 0
+            for m, ((h, w), l) in enumerate(zip(dims, logs[r])):
+                row = [int(v) for v in opened[q, at:at + int(w)]]
+                at += int(w)
+                pts = np.asarray(points[m], dtype=np.uint32).reshape(-1, dc)
+                vals = np.asarray(values[m], dtype=np.uint32).reshape(len(pts), int(w), dc)
+                if not len(pts) or not int(w):
+                    continue   # adds nothing and does not advance the running power (p3r_fri_reduce_dmat)
+                x = g * pow(pow(g, (p - 1) >> l, p), _bit_reverse(index >> (log_max - l), l), p) % p
+                s_row = E.lift(0)
+                for c, cell in enumerate(row):
+                    s_row = E.add(s_row, [a * cell % p for a in apow[c]])
+                for k, z in enumerate(pts):
+                    v_pt = E.lift(0)
+                    for c in range(int(w)):
+                        v_pt = E.add(v_pt, E.mul(apow[c], [int(t) for t in vals[k, c]]))
+                    quot = E.mul(E.sub(v_pt, s_row), E.inv(E.sub([int(t) for t in z], E.lift(x))))
+                    reduced[l][q] = E.add(reduced[l][q], E.mul(running[l], quot))
+                    running[l] = E.mul(running[l], apow[int(w)])
+    fri_verify(cfg, ch, fri_proof, [(l, np.array(reduced[l], dtype=np.uint32)) for l in heights])
+
+
 class AirValue:
     """A value of an AirBuilder program: the id of the instruction that defines it.  + - * and unary - record
     instructions; a Python int operand becomes a constant (reduced into the field)."""
@@ -292,6 +525,33 @@ def air_program_info(cfg, program, widths):
     if rc != 0:
         raise P3rError(rc, lib.p3r_last_error(None).decode())
     return {k: int(getattr(info, k)) for k, _ in _lib.P3rAirInfo._fields_}
+
+
+def air_program_eval(cfg, program, widths, local, next, log_height, zeta, public_values=(), challenges=(), alpha=None):
+    """p3r_air_program_eval on the host (no GPU): the constraint `program` at the out-of-domain point `zeta` from opened
+    values.  `local` / `next`: (sum(widths), DC) canonical words, the opened values at zeta and zeta * w_h, matrices in
+    order; `alpha`: DC words.  Returns (folded, inv_zh), DC words each: the Horner fold of the constraints with alpha and
+    1 / (zeta^h - 1).  Raises P3rError: what air_program_info refuses, index ranges, non-canonical words, and a zeta
+    with zeta^h == 1, zeta == 1 or zeta == w_h^-1."""
+    lib = _lib.load()
+    dc = 5 if cfg.challenge_degree == 5 else 4
+    arr, n = _air_insns(program)
+    ws = (C.c_size_t * max(1, len(widths)))(*[int(w) for w in widths])
+    lo, lop = _u32(np.asarray(local, dtype=np.uint32).reshape(-1))
+    nx, nxp = _u32(np.asarray(next, dtype=np.uint32).reshape(-1))
+    total = sum(int(w) for w in widths) * dc
+    if lo.size != total or nx.size != total:
+        raise P3rError(-1, "the opened values must hold sum(widths) x DC = %d words (%d and %d given)" % (total, lo.size, nx.size))
+    z, zp = _u32(np.asarray(zeta, dtype=np.uint32).reshape(dc))
+    pv, pvp = _u32(np.asarray(public_values, dtype=np.uint32).reshape(-1))
+    chs, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
+    al, alp = _u32(np.asarray(alpha, dtype=np.uint32).reshape(dc))
+    folded, inv_zh = np.zeros(dc, dtype=np.uint32), np.zeros(dc, dtype=np.uint32)
+    rc = lib.p3r_air_program_eval(C.byref(cfg), arr, n, ws, len(widths), lop, nxp, int(log_height), zp, pvp, pv.size, chp, len(chs), alp,
+                                  folded.ctypes.data_as(_lib.u32p), inv_zh.ctypes.data_as(_lib.u32p))
+    if rc != 0:
+        raise P3rError(rc, lib.p3r_last_error(None).decode())
+    return folded, inv_zh
 
 
 def lookup_program_info(cfg, program, widths):
@@ -763,6 +1023,37 @@ class Context:
                 t.free()
             for d in views + mine:
                 d.free()
+
+    def pcs_open(self, ch, rounds):
+        """TwoAdicFriPcs::open composed from public calls, all resident.  `rounds`: per commitment a tuple
+        (tree, dmats, points) - the MerkleTree of commit_device, the committed LDEs it was made from (bit-reversed rows over
+        the generator's coset, blow-up 2^log_blowup) and per matrix its (k, DC) opening points.  open_points_device gives
+        the opened values, which are observed (observe_opened_values); alpha is sampled; fri_reduce_device forms the
+        per-height reduced openings; prove_fri runs over them; every round's tree is opened at every query index with
+        MerkleTree.open_many.  Returns (values, fri_proof, input_openings): values[round][matrix] is (k, width, DC), and
+        input_openings[round] = (opened, salts or None, siblings) - what pcs_verify takes."""
+        flat_d = [d for tree, dmats, points in rounds for d in dmats]
+        flat_p = [np.asarray(pt, dtype=np.uint32).reshape(-1, self.challenge_degree) for tree, dmats, points in rounds for pt in points]
+        if len(flat_d) != len(flat_p) or not flat_d:
+            raise P3rError(-1, "pcs_open: one array of points per committed matrix")
+        flat_v = self.open_points_device(flat_d, flat_p, added_bits=self.log_blowup)
+        values, at = [], 0
+        for tree, dmats, points in rounds:
+            values.append(flat_v[at:at + len(dmats)])
+            at += len(dmats)
+        observe_opened_values(ch, values)
+        alpha = ch.sample_ext()
+        inputs = self.fri_reduce_device(flat_d, flat_p, flat_v, alpha)
+        try:
+            proof = self.prove_fri(ch, inputs)
+        finally:
+            for d in inputs:
+                d.free()
+        openings = []
+        for tree, dmats, points in rounds:
+            shift = proof.log_max_height - int(tree.log_max_height)
+            openings.append(tree.open_many([i >> shift for i in proof.query_indices]))
+        return values, proof, openings
 
     # ---- MMCS
     def commit(self, mats):
