@@ -864,6 +864,59 @@ int p3r_lookup_check_dmat(p3r_ctx* ctx, const p3r_lookup_instance* inst, size_t 
                           const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
                           p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out);
 
+/* ---- a table's multiplicity column, built on the device from resident traces ----
+ *
+ * Functions are only added: P3R_ABI_VERSION stays as it is, no op is added, and no entry above changes.
+ *
+ * Range checks, byte tables and opcode tables need a column that says how often each table row is asked for.  It belongs
+ * to the MAIN trace, so it must exist before the trace commitment; p3r_lookup_multiplicities_dmat joins a table against
+ * its queries where the traces already lie.  `table` and the `queries` are lookup programs with their traces, exactly as
+ * p3r_lookup_check_dmat takes instances: the same validation, the same slots (term t of row r) and the same record order,
+ * with the table's slots before those of query 0, query 1, ...
+ *
+ * Keys.  The key of a slot is the value of its LOOKUP denominator, lifted to the challenge field, as in the check; nothing
+ * is inverted.
+ * Table slots.  Slot (r, t) of the table OFFERS its key when the multiplicity value of that term is non-zero.  The value
+ * is otherwise unused: it is an enable flag, with which a caller switches off padding rows.
+ * Query records.  Every LOOKUP term of a query with a non-zero multiplicity is a record (key, m).  Query multiplicities
+ * must be statically typed base values - the output is a base column.
+ * Output.  *out is a fresh h_T x n_terms_T matrix the caller frees, of the form every p3r_dmat has.  out[r][t] = the sum
+ * modulo p of m over all query records whose key is the key of table slot (r, t), if (r, t) is the first offering table
+ * slot with that key in (row, term) order; every other cell is 0: later duplicates, disabled slots, keys nobody asks
+ * for.  It is a trace column like any other: it goes to p3r_logup_program_dmat, the LDE, the commit and
+ * p3r_check_program_dmat as it is, and the table's own lookup program then uses its negation as the multiplicity.
+ * Misses.  A key carried by query records is missing when no table slot offers it and its multiplicities do not sum to
+ * zero.  *n_missing_out counts them; `missing` receives the first min(cap, count), ordered by their first query record:
+ * instance is the index into `queries`, row and term the place of the first record, n_records, denominator and net as
+ * in the check.  A non-zero count is a RESULT: the call returns P3R_OK and *out is produced all the same.
+ * The call WAITS for the stream.  n_queries == 0 is legal and gives a zero column.
+ *
+ * WHICH CHALLENGES.  The column is built before the transcript has produced any LogUp challenge, so the `challenges`
+ * passed here are the CALLER'S OWN, not the transcript's; they only have to make equal tuples equal keys and different
+ * tuples different keys.
+ *   - With the basis elements 1, X, .., X^(DC-1) as challenges, a tuple (a_0, .., a_(k-1)) of k <= DC base values under the
+ *     denominator sum_j X^j * a_j is its own key: the join is exact.
+ *   - A single-field key c - v is exact for any constant c.
+ *   - A longer tuple is joined under a challenge beta the caller draws privately, key = sum_j beta^j * a_j.  Two different
+ *     tuples of length k share a key only if beta is a root of a non-zero polynomial of degree below k: with N = T + Q table
+ *     slots and query records, Pr[two different tuples share a key] <= N * (N - 1) / 2 * (k - 1) / p^DC over the choice of
+ *     beta, as long as the traces do not depend on beta.
+ *
+ * Refusals, with a message, before anything is allocated or launched; the context stays usable.  Each instance for what
+ * p3r_logup_program_dmat would refuse it for (the message names "table" or "query i"); a NULL table, out or
+ * n_missing_out, a NULL missing with cap > 0 (P3R_EINVAL); more than P3R_LOOKUP_CHECK_MAX_RECORDS term slots summed over
+ * the table and the queries, a query LOOKUP whose multiplicity is of extension type, zk contexts (P3R_EUNSUPPORTED).
+ * The pass is the check's - records, compaction, the stable sort by key, head marks, exclusive sums of 64-bit words, here of
+ * coefficient word 0 with the table's slots counted as zero - and ends in one kernel in which the head of every run
+ * either stores the run's sum to its cell of the zeroed output (a table slot: one writer per cell, no atomics) or is
+ * flagged as a miss (a query slot). */
+int p3r_lookup_multiplicities_dmat(p3r_ctx* ctx,
+                                   const p3r_lookup_instance* table,                    /* the table that offers keys */
+                                   const p3r_lookup_instance* queries, size_t n_queries,
+                                   const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
+                                   p3r_dmat** out,                                      /* fresh h_T x n_terms_T, the caller frees */
+                                   p3r_lookup_imbalance* missing, size_t cap, uint64_t* n_missing_out);
+
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *
  * p3r_prep_create  == ProverData::from_airs_and_degrees + CircuitProverData::new as called by

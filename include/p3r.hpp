@@ -404,6 +404,36 @@ inline LookupCheck check_lookups(const Context& ctx, const std::vector<LookupTab
   return out;
 }
 
+// The multiplicity column of a table against its queries (p3r.h: p3r_lookup_multiplicities_dmat).  A term of `table`
+// offers its key - its denominator value - where its multiplicity value is non-zero; a term of a query with a non-zero
+// base multiplicity m asks for its key m times.  `column` is the h x n_terms matrix of the table, which the caller frees:
+// the first offering slot of a key holds the sum of what is asked of it, every other cell 0.  `missing` holds at most `cap`
+// of the `n_missing` keys that are asked for and offered by no slot, those whose first query records come earliest
+// (instance: the index into `queries`).  The column belongs to the main trace, which is committed before the transcript
+// yields a challenge: `challenges` are the caller's own (p3r.h says which make the join exact).  Waits for the device.
+struct LookupMultiplicities {
+  p3r_dmat* column;
+  uint64_t n_missing;
+  std::vector<p3r_lookup_imbalance> missing;
+};
+inline LookupMultiplicities lookup_multiplicities(const Context& ctx, const LookupTable& table, const std::vector<LookupTable>& queries,
+                                                  const std::vector<uint32_t>& challenges = {}, size_t cap = 16) {
+  const size_t dc = ctx.config().challenge_degree ? ctx.config().challenge_degree : 4;
+  if (challenges.size() % dc) throw Error(P3R_EINVAL, "challenges are DC words each");
+  auto instance = [](const LookupTable& t) {
+    return p3r_lookup_instance{t.program->insns().data(), t.program->insns().size(), t.mats.data(), t.mats.size(),
+                               t.public_values.data(), t.public_values.size()};
+  };
+  const p3r_lookup_instance tab = instance(table);
+  std::vector<p3r_lookup_instance> qs;
+  for (const LookupTable& q : queries) qs.push_back(instance(q));
+  LookupMultiplicities out{nullptr, 0, std::vector<p3r_lookup_imbalance>(cap)};
+  ctx.check(p3r_lookup_multiplicities_dmat(ctx.raw(), &tab, qs.data(), qs.size(), challenges.data(), challenges.size() / dc, &out.column,
+                                           out.missing.data(), cap, &out.n_missing));
+  out.missing.resize((size_t)std::min<uint64_t>(cap, out.n_missing));
+  return out;
+}
+
 // DuplexChallenger<F, Perm16, 16, 8> of circuit-prover/src/config.rs over the context's Poseidon2 constants (p3r.h:
 // p3r_challenger).  Host state, except the proof-of-work search of grind.  Words are canonical.
 class DuplexChallenger {

@@ -297,6 +297,10 @@ SIGNATURES = {
                                          C.c_size_t, C.POINTER(P3rCheckReport), u32p, C.POINTER(C.c_uint64)]),
     "p3r_lookup_check_dmat": (C.c_int, [vp, C.POINTER(P3rLookupInstance), C.c_size_t, u32p, C.c_size_t, C.POINTER(P3rLookupImbalance),
                                         C.c_size_t, C.POINTER(C.c_uint64)]),
+    # a table's multiplicity column, joined against its queries on the device
+    "p3r_lookup_multiplicities_dmat": (C.c_int, [vp, C.POINTER(P3rLookupInstance), C.POINTER(P3rLookupInstance), C.c_size_t, u32p,
+                                                 C.c_size_t, C.POINTER(vp), C.POINTER(P3rLookupImbalance), C.c_size_t,
+                                                 C.POINTER(C.c_uint64)]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

@@ -924,6 +924,29 @@ int p3r_lookup_check_dmat(p3r_ctx* ctx, const p3r_lookup_instance* inst, size_t 
     P3R_FIELD_CALL(ctx, lookup_check, ctx, is, challenges, n_challenges, out, cap, n_unbalanced_out);
   });
 }
+int p3r_lookup_multiplicities_dmat(p3r_ctx* ctx, const p3r_lookup_instance* table, const p3r_lookup_instance* queries, size_t n_queries,
+                                   const uint32_t* challenges, size_t n_challenges, p3r_dmat** out, p3r_lookup_imbalance* missing,
+                                   size_t cap, uint64_t* n_missing_out) {
+  return guard(ctx, [&] {
+    if (out) *out = nullptr;
+    if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
+    if (!table) fail(P3R_EINVAL, "table is NULL");
+    if (!out) fail(P3R_EINVAL, "out is NULL");
+    if (n_queries && !queries) fail(P3R_EINVAL, "queries is NULL");
+    std::vector<LookupCheckInstance> is(1 + n_queries);   // the table first
+    for (size_t p = 0; p <= n_queries; ++p) {
+      const p3r_lookup_instance& in = p ? queries[p - 1] : *table;
+      const std::string who = p ? "query " + std::to_string(p - 1) : std::string("table");
+      if (in.n_mats && !in.mats) fail(P3R_EINVAL, "%s: mats is NULL", who.c_str());
+      is[p] = LookupCheckInstance{in.prog, in.n_insns, {}, in.public_values, in.n_public};
+      for (size_t i = 0; i < in.n_mats; ++i) {
+        if (!in.mats[i]) fail(P3R_EINVAL, "%s: matrix %zu is NULL", who.c_str(), i);
+        is[p].mats.push_back(in.mats[i]);
+      }
+    }
+    *out = P3R_FIELD_CALL(ctx, lookup_multiplicities, ctx, is, challenges, n_challenges, missing, cap, n_missing_out).release();
+  });
+}
 
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,
                          uint32_t* cap_out, p3r_tree** tree_out) {

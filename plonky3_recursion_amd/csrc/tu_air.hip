@@ -7,6 +7,8 @@
 // So do the two checks of a caller's traces: p3r_check_program_dmat (k_check_program: the constraints on the trace domain,
 // a first failing row and a count per constraint) and p3r_lookup_check_dmat (k_lookup_records, then the stable radix sort
 // and the sums of device_prims.hip.h: the keys of the bus whose multiplicities do not cancel).
+// p3r_lookup_multiplicities_dmat is the same pass (LookupPass) with another end: k_lookup_scatter gives every key's first
+// table slot the sum its queries ask for - the multiplicity column of a table - and reports the keys no table slot offers.
 #include <algorithm>
 
 #include "device_prims.hip.h"
@@ -401,77 +403,99 @@ inline DevBuf marked_list(p3r_ctx* ctx, const uint32_t* marks, size_t n, DevBuf&
   return list;
 }
 
-template <class PP, int DC>
-void lookup_check_dc(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges,
-                     p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out) {
-  // ---- everything that is refused, before anything is allocated or launched
-  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the lookup check does not serve zk contexts (their traces are randomised and their domains doubled)");
-  if (insts.empty()) fail(P3R_EINVAL, "n_inst == 0: no table on the bus");
-  if (!n_unbalanced_out) fail(P3R_EINVAL, "n_unbalanced_out is NULL");
-  if (cap && !out) fail(P3R_EINVAL, "out is NULL with cap > 0");
-  std::vector<TraceProgram> tps;
-  std::vector<size_t> base(1, 0);   // first slot of every instance, and the total
-  for (size_t p = 0; p < insts.size(); ++p) {
-    const LookupCheckInstance& in = insts[p];
-    try {
-      tps.push_back(trace_program<PP, DC>(in.prog, in.n_insns, in.mats, in.publics, in.n_public, challenges, n_challenges, AIR_MODE_LOOKUP));
-    } catch (const Error& e) {
-      fail(e.code, "instance %zu: %s", p, e.what());
-    }
-    const size_t slots = tps[p].h * tps[p].plan.lookup.n_terms;   // below 2^27 * 2^31
-    if (slots > P3R_LOOKUP_CHECK_MAX_RECORDS || base[p] + slots > P3R_LOOKUP_CHECK_MAX_RECORDS)
-      fail(P3R_EUNSUPPORTED, "more than P3R_LOOKUP_CHECK_MAX_RECORDS (2^28) term slots: rows x terms, summed over the instances");
-    base.push_back(base[p] + slots);
+// the same word with the slots below `floor` - the table's, in the join - counted as zero
+struct SortedWordFrom {
+  const uint32_t* words;
+  const uint32_t* order;
+  uint32_t floor;
+  __device__ uint64_t operator()(size_t i) const {
+    const uint32_t s = order[i];
+    return s >= floor ? words[s] : 0u;
   }
-  const size_t S = base.back();
-  hipStream_t s = ctx->stream;
+};
 
-  // ---- the records: one launch per instance
-  DevBuf den((size_t)DC * S), mul((size_t)DC * S), mark(S);
-  {
-    ProfScope ps(ctx, "lookup_check_records");
+// What the lookup check and the multiplicity join share: the instances validated and their slots numbered (plan), every
+// term recorded, the records among the slots ordered by key (sorted_records), the head of every key's run marked and the
+// exclusive sums of the multiplicity words taken over the sorted records (run_sums).  The entries differ in what they
+// refuse about their own arguments, in what a run's head then does, and in their words.
+struct LookupPassWords {
+  const char *first, *rest;   // "instance" / "instance", or "table" / "query": how a refused instance is named
+  const char* too_many;
+  const char *scope_records, *scope_sort;
+};
+template <class PP, int DC>
+struct LookupPass {
+  std::vector<TraceProgram> tps;
+  std::vector<size_t> base{0};   // first slot of every instance, and the total
+  size_t S = 0, n = 0;           // slots, records
+  DevBuf den, mul, order;        // [DC][S], [DC][S]; order[i]: the slot of the record at sorted position i
+  DevBuf head, head_rank, heads, prefix[DC], no_sums;
+  LookupRuns<DC> runs{};
+
+  // ---- the refusals about the instances, before anything is allocated or launched
+  void plan(const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges, const LookupPassWords& w,
+            bool first_is_table) {
     for (size_t p = 0; p < insts.size(); ++p) {
       const LookupCheckInstance& in = insts[p];
-      const TraceProgram& tp = tps[p];
-      const AirCompiled code = air_compile<PP>(tp.plan, in.prog, in.n_insns, tp.widths.data(), tp.widths.size(), DC, in.publics, challenges);
-      ProgramBlob blob(0, code, in.mats, tp.n_cols);
-      blob.upload(ctx);
-      AirRecordArgs a{};
-      a.insns = blob.insns();
-      a.ext_consts = blob.ext_consts();
-      a.cols = blob.cols();
-      a.den = den.p;
-      a.mul = mul.p;
-      a.mark = mark.p;
-      a.n_slots = S;
-      a.base = base[p];
-      a.n_terms = tp.plan.lookup.n_terms;
-      a.n_insns = (uint32_t)code.insns.size();
-      a.log_h = tp.log_h;
-      // rows r < h of every input column are read; slot base + r * n_terms + t with r < h and t < n_terms - the TERMs of
-      // the stream, which air_plan counted - lies in [base_p, base_p+1), so below S: words k * S + slot < DC * S of den and
-      // mul and word slot of mark.  Every slot of the instance is written: nothing is read uninitialised afterwards.
-      const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
-      if (tp.lds > 48 * 1024)
-        P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lookup_records<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kAirMaxLdsBytes));
-      hipLaunchKernelGGL((k_lookup_records<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, s, a);
-      P3R_HIP(hipGetLastError());
-      // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
+      try {
+        tps.push_back(trace_program<PP, DC>(in.prog, in.n_insns, in.mats, in.publics, in.n_public, challenges, n_challenges, AIR_MODE_LOOKUP));
+      } catch (const Error& e) {
+        if (first_is_table && p == 0) fail(e.code, "%s: %s", w.first, e.what());
+        fail(e.code, "%s %zu: %s", w.rest, first_is_table ? p - 1 : p, e.what());
+      }
+      const size_t slots = tps[p].h * tps[p].plan.lookup.n_terms;   // below 2^27 * 2^31
+      if (slots > P3R_LOOKUP_CHECK_MAX_RECORDS || base[p] + slots > P3R_LOOKUP_CHECK_MAX_RECORDS) fail(P3R_EUNSUPPORTED, "%s", w.too_many);
+      base.push_back(base[p] + slots);
     }
+    S = base.back();
   }
 
-  // ---- the records among the slots, ordered by key
-  *n_unbalanced_out = 0;
-  size_t n = 0;
-  DevBuf slot_rank(S + 1);
-  DevBuf order = marked_list(ctx, mark.p, S, slot_rank, &n);   // order[i]: the slot of the record at position i
-  slot_rank.release();
-  mark.release();
-  if (!n) return;
-  const unsigned blocks_n = prims::blocks_of(n);
-  {
-    ProfScope ps(ctx, "lookup_check_sort");
+  // ---- the records (one launch per instance), then the records among the slots, ordered by key; n: their number
+  void sorted_records(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, const LookupPassWords& w) {
+    hipStream_t s = ctx->stream;
+    den.alloc((size_t)DC * S);
+    mul.alloc((size_t)DC * S);
+    DevBuf mark(S);
+    {
+      ProfScope ps(ctx, w.scope_records);
+      for (size_t p = 0; p < insts.size(); ++p) {
+        const LookupCheckInstance& in = insts[p];
+        const TraceProgram& tp = tps[p];
+        const AirCompiled code = air_compile<PP>(tp.plan, in.prog, in.n_insns, tp.widths.data(), tp.widths.size(), DC, in.publics, challenges);
+        ProgramBlob blob(0, code, in.mats, tp.n_cols);
+        blob.upload(ctx);
+        AirRecordArgs a{};
+        a.insns = blob.insns();
+        a.ext_consts = blob.ext_consts();
+        a.cols = blob.cols();
+        a.den = den.p;
+        a.mul = mul.p;
+        a.mark = mark.p;
+        a.n_slots = S;
+        a.base = base[p];
+        a.n_terms = tp.plan.lookup.n_terms;
+        a.n_insns = (uint32_t)code.insns.size();
+        a.log_h = tp.log_h;
+        // rows r < h of every input column are read; slot base + r * n_terms + t with r < h and t < n_terms - the TERMs of
+        // the stream, which air_plan counted - lies in [base_p, base_p+1), so below S: words k * S + slot < DC * S of den and
+        // mul and word slot of mark.  Every slot of the instance is written: nothing is read uninitialised afterwards.
+        const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
+        if (tp.lds > 48 * 1024)
+          P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lookup_records<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)kAirMaxLdsBytes));
+        hipLaunchKernelGGL((k_lookup_records<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, s, a);
+        P3R_HIP(hipGetLastError());
+        // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
+      }
+    }
+    {
+      DevBuf slot_rank(S + 1);
+      order = marked_list(ctx, mark.p, S, slot_rank, &n);
+    }
+    mark.release();
+    if (!n) return;
+    const unsigned blocks_n = prims::blocks_of(n);
+    ProfScope ps(ctx, w.scope_sort);
     // least significant word first, every word a canonical residue below 2^31; the sort is stable, so records of one key
     // stay in record order and the first of a run is the key's first record
     DevBuf keys(n), keys_sorted(n), order_next(n);
@@ -482,31 +506,44 @@ void lookup_check_dc(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts
     }
     P3R_HIP(hipGetLastError());
   }
-  uint64_t n_unbalanced = 0;
-  std::vector<uint32_t> answer;
-  {
-    ProfScope ps(ctx, "lookup_check_sums");
-    // ---- the runs of equal keys and their sums
-    DevBuf head(n), head_rank(n + 1), heads(n), flag(n), flag_rank(n + 1);
-    hipLaunchKernelGGL((k_lookup_heads<DC>), dim3(blocks_n), dim3(prims::kPB), 0, s, den.p, S, order.p, n, head.p);
+
+  // ---- the runs of equal keys and their sums (n > 0): the multiplicity words of coefficients k < n_words, with the slots
+  // below `floor` counted as zero; the other coefficients sum to zero (their multiplicities are base values)
+  void run_sums(p3r_ctx* ctx, int n_words, uint32_t floor) {
+    hipStream_t s = ctx->stream;
+    head.alloc(n);
+    head_rank.alloc(n + 1);
+    heads.alloc(n);
+    hipLaunchKernelGGL((k_lookup_heads<DC>), dim3(prims::blocks_of(n)), dim3(prims::kPB), 0, s, den.p, S, order.p, n, head.p);
     prims::select_marked(s, head.p, n, head_rank.p, heads.p);   // as many heads as keys: the first of them are written
-    DevBuf prefix[DC];
-    LookupRuns<DC> runs{};
     runs.head_rank = head_rank.p;
     runs.heads = heads.p;
     runs.n = n;
+    if (n_words < DC) {
+      no_sums.alloc(2 * (n + 1));
+      P3R_HIP(hipMemsetAsync(no_sums.p, 0, 8 * (n + 1), s));
+    }
     for (int k = 0; k < DC; ++k) {
+      if (k >= n_words) {
+        runs.prefix[k] = reinterpret_cast<const uint64_t*>(no_sums.p);
+        continue;
+      }
       prefix[k].alloc(2 * (n + 1));
       uint64_t* pk = reinterpret_cast<uint64_t*>(prefix[k].p);
-      prims::ranks_of<uint64_t>(s, SortedWord{mul.p + (size_t)k * S, order.p}, n, pk);
+      if (floor) prims::ranks_of<uint64_t>(s, SortedWordFrom{mul.p + (size_t)k * S, order.p, floor}, n, pk);
+      else prims::ranks_of<uint64_t>(s, SortedWord{mul.p + (size_t)k * S, order.p}, n, pk);
       runs.prefix[k] = pk;
     }
-    hipLaunchKernelGGL((k_lookup_flag<DC>), dim3(blocks_n), dim3(prims::kPB), 0, s, runs, head.p, PP::P, flag.p);
     P3R_HIP(hipGetLastError());
-    // ---- the unbalanced heads, ordered by their first record
+  }
+
+  // ---- the keys at the marked heads flag[0 .. n), ordered by their first record: their number, and the first `cap` of them
+  // as k_lookup_report writes them (waits for the stream)
+  uint64_t report(p3r_ctx* ctx, const uint32_t* flag, size_t cap, std::vector<uint32_t>& answer) {
+    hipStream_t s = ctx->stream;
     size_t nu = 0;
-    DevBuf pos = marked_list(ctx, flag.p, n, flag_rank, &nu);   // sorted positions of the unbalanced heads
-    n_unbalanced = nu;
+    DevBuf flag_rank(n + 1);
+    DevBuf pos = marked_list(ctx, flag, n, flag_rank, &nu);   // sorted positions of the marked heads
     const size_t n_out = std::min(cap, nu);
     if (n_out) {
       DevBuf first_slot(nu), first_sorted(nu), pos_sorted(nu), d_answer(n_out * kImbalanceWords);
@@ -519,22 +556,130 @@ void lookup_check_dc(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts
       answer.resize(n_out * kImbalanceWords);
       P3R_HIP(fetch_small(ctx, d_answer.p, answer.size(), answer.data()));   // waits for the stream
     }
+    return nu;
   }
-  *n_unbalanced_out = n_unbalanced;
-  for (size_t j = 0; j * kImbalanceWords < answer.size(); ++j) {   // at most `cap` entries: no loop over records
-    const uint32_t* o = answer.data() + j * kImbalanceWords;
-    const size_t p = (size_t)(std::upper_bound(base.begin(), base.end(), (size_t)o[0]) - base.begin()) - 1;
-    const uint32_t n_terms = tps[p].plan.lookup.n_terms;
-    p3r_lookup_imbalance& e = out[j];
-    e.instance = (uint32_t)p;
-    e.row = (uint32_t)((o[0] - base[p]) / n_terms);
-    e.term = (uint32_t)((o[0] - base[p]) % n_terms);
-    e.n_records = o[1];
-    for (int k = 0; k < kMaxAirDC; ++k) {
-      e.denominator[k] = o[2 + k];
-      e.net[k] = o[2 + kMaxAirDC + k];
+
+  // the host's half of the report: slots back to (instance, row, term); first_instance: what instance 0 of the report is
+  void entries(const std::vector<uint32_t>& answer, size_t first_instance, p3r_lookup_imbalance* out) const {
+    for (size_t j = 0; j * kImbalanceWords < answer.size(); ++j) {   // at most `cap` entries: no loop over records
+      const uint32_t* o = answer.data() + j * kImbalanceWords;
+      const size_t p = (size_t)(std::upper_bound(base.begin(), base.end(), (size_t)o[0]) - base.begin()) - 1;
+      const uint32_t n_terms = tps[p].plan.lookup.n_terms;
+      p3r_lookup_imbalance& e = out[j];
+      e.instance = (uint32_t)(p - first_instance);
+      e.row = (uint32_t)((o[0] - base[p]) / n_terms);
+      e.term = (uint32_t)((o[0] - base[p]) % n_terms);
+      e.n_records = o[1];
+      for (int k = 0; k < kMaxAirDC; ++k) {
+        e.denominator[k] = o[2 + k];
+        e.net[k] = o[2 + kMaxAirDC + k];
+      }
     }
   }
+};
+
+template <class PP, int DC>
+void lookup_check_dc(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges,
+                     p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out) {
+  // ---- everything that is refused, before anything is allocated or launched
+  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the lookup check does not serve zk contexts (their traces are randomised and their domains doubled)");
+  if (insts.empty()) fail(P3R_EINVAL, "n_inst == 0: no table on the bus");
+  if (!n_unbalanced_out) fail(P3R_EINVAL, "n_unbalanced_out is NULL");
+  if (cap && !out) fail(P3R_EINVAL, "out is NULL with cap > 0");
+  const LookupPassWords words{"instance", "instance",
+                              "more than P3R_LOOKUP_CHECK_MAX_RECORDS (2^28) term slots: rows x terms, summed over the instances",
+                              "lookup_check_records", "lookup_check_sort"};
+  LookupPass<PP, DC> pass;
+  pass.plan(insts, challenges, n_challenges, words, false);
+
+  pass.sorted_records(ctx, insts, challenges, words);
+  *n_unbalanced_out = 0;
+  const size_t n = pass.n;
+  if (!n) return;
+  uint64_t n_unbalanced = 0;
+  std::vector<uint32_t> answer;
+  {
+    ProfScope ps(ctx, "lookup_check_sums");
+    pass.run_sums(ctx, DC, 0);
+    DevBuf flag(n);
+    hipLaunchKernelGGL((k_lookup_flag<DC>), dim3(prims::blocks_of(n)), dim3(prims::kPB), 0, ctx->stream, pass.runs, pass.head.p, PP::P, flag.p);
+    P3R_HIP(hipGetLastError());
+    n_unbalanced = pass.report(ctx, flag.p, cap, answer);   // the unbalanced heads, ordered by their first record
+  }
+  *n_unbalanced_out = n_unbalanced;
+  pass.entries(answer, 0, out);
+}
+
+// ---- the multiplicity join (p3r_lookup_multiplicities_dmat): the column that balances a table against its queries.
+// The table's slots are numbered first, and its enable flag is the record mark: the sort is stable, so the first table
+// slot that offers a key heads the key's run, and a run headed by a query slot has no table slot in it.
+
+// Sorted position i, if it heads a run: a table slot (below n_table) takes the run's sum - the table's own words count as
+// zero in it - into its cell of the zeroed h x n_terms output (Montgomery, [term][row]); one head per run and one cell
+// per slot, so every cell has at most one writer.  A query slot whose run does not cancel is flagged as a miss.
+template <class PP, int DC>
+__global__ void __launch_bounds__(prims::kPB) k_lookup_scatter(LookupRuns<DC> runs, const uint32_t* __restrict__ head,
+                                                               const uint32_t* __restrict__ order, uint32_t n_table, uint32_t n_terms,
+                                                               size_t h, uint32_t* __restrict__ out, uint32_t* __restrict__ flag) {
+  const size_t i = (size_t)blockIdx.x * prims::kPB + threadIdx.x;
+  if (i >= runs.n) return;
+  uint32_t missing = 0;
+  if (head[i]) {
+    const uint32_t s = order[i];
+    const uint32_t net = runs.net(0, i, runs.end_of(i), PP::P);
+    if (s < n_table) out[(size_t)(s % n_terms) * h + s / n_terms] = Fp<PP>::from_canonical(net).v;   // s < n_table = h * n_terms
+    else missing = net != 0;
+  }
+  flag[i] = missing;
+}
+
+template <class PP, int DC>
+std::unique_ptr<p3r_dmat> lookup_multiplicities_dc(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges,
+                                                   size_t n_challenges, p3r_lookup_imbalance* missing, size_t cap, uint64_t* n_missing_out) {
+  // ---- everything that is refused, before anything is allocated or launched.  insts[0] is the table.
+  if (ctx->cfg.zk)
+    fail(P3R_EUNSUPPORTED, "the multiplicity join does not serve zk contexts (their traces are randomised and their domains doubled)");
+  if (!n_missing_out) fail(P3R_EINVAL, "n_missing_out is NULL");
+  if (cap && !missing) fail(P3R_EINVAL, "missing is NULL with cap > 0");
+  const LookupPassWords words{"table", "query",
+                              "more than P3R_LOOKUP_CHECK_MAX_RECORDS (2^28) term slots: rows x terms, summed over the table and the queries",
+                              "lookup_mult_records", "lookup_mult_sort"};
+  LookupPass<PP, DC> pass;
+  pass.plan(insts, challenges, n_challenges, words, true);
+  for (size_t q = 1; q < insts.size(); ++q)
+    for (size_t i = 0; i < insts[q].n_insns; ++i)
+      if (insts[q].prog[i].op == P3R_AIR_LOOKUP && pass.tps[q].plan.is_ext[insts[q].prog[i].a])
+        fail(P3R_EUNSUPPORTED, "query %zu: instruction %zu: a multiplicity of extension type; the column of counts is a base column", q - 1, i);
+  const size_t h = pass.tps[0].h, n_terms = pass.tps[0].plan.lookup.n_terms, n_table = pass.base[1];
+
+  hipStream_t s = ctx->stream;
+  std::unique_ptr<p3r_dmat> out = dmat_alloc(h, n_terms);   // [n_terms][h]
+  P3R_HIP(hipMemsetAsync(out->d, 0, 4 * h * n_terms, s));
+  *n_missing_out = 0;
+  pass.sorted_records(ctx, insts, challenges, words);
+  const size_t n = pass.n;
+  if (!n) {
+    P3R_HIP(hipStreamSynchronize(s));
+    return out;
+  }
+  uint64_t n_missing = 0;
+  std::vector<uint32_t> answer;
+  {
+    ProfScope ps(ctx, "lookup_mult_sums");
+    pass.run_sums(ctx, 1, (uint32_t)n_table);
+  }
+  {
+    ProfScope ps(ctx, "lookup_mult_scatter");
+    DevBuf flag(n);
+    // order[i] < S; a head below n_table = h * n_terms writes word (s % n_terms) * h + s / n_terms < n_terms * h of the output
+    hipLaunchKernelGGL((k_lookup_scatter<PP, DC>), dim3(prims::blocks_of(n)), dim3(prims::kPB), 0, s, pass.runs, pass.head.p, pass.order.p,
+                       (uint32_t)n_table, (uint32_t)n_terms, h, out->d, flag.p);
+    P3R_HIP(hipGetLastError());
+    n_missing = pass.report(ctx, flag.p, cap, answer);   // the misses, ordered by their first record; waits for the stream
+  }
+  *n_missing_out = n_missing;
+  pass.entries(answer, 1, missing);
+  return out;
 }
 
 }  // namespace
@@ -587,6 +732,16 @@ void lookup_check(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, c
   lookup_check_dc<PP, 4>(ctx, insts, challenges, n_challenges, out, cap, n_unbalanced_out);
 }
 
+template <class PP>
+std::unique_ptr<p3r_dmat> lookup_multiplicities(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges,
+                                                size_t n_challenges, p3r_lookup_imbalance* missing, size_t cap, uint64_t* n_missing_out) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>) return lookup_multiplicities_dc<PP, 5>(ctx, insts, challenges, n_challenges, missing, cap, n_missing_out);
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  return lookup_multiplicities_dc<PP, 4>(ctx, insts, challenges, n_challenges, missing, cap, n_missing_out);
+}
+
 #define P3R_AIR_INSTANCE(PP)                                                                                                     \
   template std::vector<std::unique_ptr<p3r_dmat>> quotient_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t,                    \
                                                                        const std::vector<const p3r_dmat*>&, uint32_t, uint32_t, \
@@ -605,7 +760,9 @@ P3R_LOGUP_INSTANCE(BabyBearParams)
   template void check_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&, const uint32_t*, size_t,    \
                                   const uint32_t*, size_t, p3r_check_report*, uint32_t*, uint64_t*);                                      \
   template void lookup_check<PP>(p3r_ctx*, const std::vector<LookupCheckInstance>&, const uint32_t*, size_t, p3r_lookup_imbalance*,        \
-                                 size_t, uint64_t*);
+                                 size_t, uint64_t*);                                                                                      \
+  template std::unique_ptr<p3r_dmat> lookup_multiplicities<PP>(p3r_ctx*, const std::vector<LookupCheckInstance>&, const uint32_t*, size_t, \
+                                                               p3r_lookup_imbalance*, size_t, uint64_t*);
 P3R_CHECK_INSTANCE(KoalaBearParams)
 P3R_CHECK_INSTANCE(BabyBearParams)
 #undef P3R_CHECK_INSTANCE

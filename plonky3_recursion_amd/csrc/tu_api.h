@@ -151,6 +151,14 @@ struct LookupCheckInstance {
 template <class PP>
 void lookup_check(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges,
                   p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out);
+// The multiplicity column of a table (tu_air.hip): insts[0] is the table, the others its queries.  Returns the fresh
+// h_T x n_terms_T matrix in which the first table slot that offers a key holds the sum of the query multiplicities of that
+// key, every other cell 0; writes the number of keys that are asked for (net non-zero) and offered by no table slot, and
+// the min(cap, number) of them whose first records come earliest.  Refuses before anything is allocated or launched;
+// waits for the stream.
+template <class PP>
+std::unique_ptr<p3r_dmat> lookup_multiplicities(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges,
+                                                size_t n_challenges, p3r_lookup_imbalance* missing, size_t cap, uint64_t* n_missing_out);
 
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>

@@ -504,6 +504,27 @@ class AirBuilder:
         return np.array(self.insns, dtype=np.uint32).reshape(-1, 3)
 
 
+def _lookup_instances(instances):
+    """(P3rLookupInstance array, what its pointers keep alive) for (program, dmats[, public_values]) tuples."""
+    arr = (_lib.P3rLookupInstance * max(1, len(instances)))()
+    keep = []
+    for k, inst in enumerate(instances):
+        program, dmats = inst[0], inst[1]
+        insns, n = _air_insns(program)
+        mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+        pv, pvp = _u32(np.asarray(inst[2] if len(inst) > 2 else (), dtype=np.uint32).reshape(-1))
+        keep.append((insns, mats, pv))
+        arr[k].prog, arr[k].n_insns = insns, n
+        arr[k].mats, arr[k].n_mats = mats, len(dmats)
+        arr[k].public_values, arr[k].n_public = pvp, pv.size
+    return arr, keep
+
+
+def _lookup_entries(out, n, dc):
+    return [{"instance": int(e.instance), "row": int(e.row), "term": int(e.term), "n_records": int(e.n_records),
+             "denominator": [int(v) for v in e.denominator[:dc]], "net": [int(v) for v in e.net[:dc]]} for e in out[:n]]
+
+
 def _air_insns(program):
     prog = program.program() if isinstance(program, AirBuilder) else np.ascontiguousarray(program, dtype=np.uint32).reshape(-1, 3)
     arr = (_lib.P3rAirInsn * max(1, len(prog)))()
@@ -924,24 +945,34 @@ class Context:
         Waits for the device."""
         dc = self.challenge_degree
         ch, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
-        arr = (_lib.P3rLookupInstance * max(1, len(instances)))()
-        keep = []   # what the structs point to
-        for k, inst in enumerate(instances):
-            program, dmats = inst[0], inst[1]
-            insns, n = _air_insns(program)
-            mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
-            pv, pvp = _u32(np.asarray(inst[2] if len(inst) > 2 else (), dtype=np.uint32).reshape(-1))
-            keep.append((insns, mats, pv))
-            arr[k].prog, arr[k].n_insns = insns, n
-            arr[k].mats, arr[k].n_mats = mats, len(dmats)
-            arr[k].public_values, arr[k].n_public = pvp, pv.size
+        arr, keep = _lookup_instances(instances)
         out = (_lib.P3rLookupImbalance * max(1, int(cap)))()
         count = C.c_uint64()
         self.check(self.lib.p3r_lookup_check_dmat(self.h, arr, len(instances), chp, len(ch), out, int(cap), C.byref(count)))
-        entries = [{"instance": int(e.instance), "row": int(e.row), "term": int(e.term), "n_records": int(e.n_records),
-                    "denominator": [int(v) for v in e.denominator[:dc]], "net": [int(v) for v in e.net[:dc]]}
-                   for e in out[:min(int(cap), count.value)]]
-        return count.value, entries
+        return count.value, _lookup_entries(out, min(int(cap), count.value), dc)
+
+    def lookup_multiplicities_device(self, table, queries, challenges=(), cap=16):
+        """The multiplicity column of `table` against its `queries`, built on the device.  An instance is (program, dmats) or
+        (program, dmats, public_values), as lookup_check_device takes it; the key of a term is its denominator value under
+        `challenges` ((n, DC) canonical words).  A table term OFFERS its key where its multiplicity value is non-zero (an
+        enable flag, otherwise unused); a query term with a non-zero multiplicity m - a base value - asks for its key m
+        times.  Returns (DeviceMatrix, n_missing, entries): the new (h_table, n_terms_table) matrix holds, at the first
+        offering table slot of a key in (row, term) order, the sum modulo p of the m asked of that key, and 0 everywhere
+        else; n_missing counts the keys that are asked for (net non-zero) and offered by no table slot, and entries are the
+        min(cap, n_missing) of them whose first query records come earliest, as lookup_check_device's, `instance` being the
+        index into `queries`.  The column is part of the main trace, which is committed before the transcript yields any
+        challenge: `challenges` are the caller's own - with the basis elements 1, X, .. a tuple of up to DC base fields is
+        its own key and the join is exact (p3r.h).  Waits for the device."""
+        dc = self.challenge_degree
+        ch, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
+        tab, keep_t = _lookup_instances([table])
+        qs, keep_q = _lookup_instances(queries)
+        missing = (_lib.P3rLookupImbalance * max(1, int(cap)))()
+        count = C.c_uint64()
+        out = C.c_void_p()
+        self.check(self.lib.p3r_lookup_multiplicities_dmat(self.h, tab, qs, len(queries), chp, len(ch), C.byref(out), missing, int(cap),
+                                                           C.byref(count)))
+        return DeviceMatrix(self, self.ptr(out.value)), count.value, _lookup_entries(missing, min(int(cap), count.value), dc)
 
     # ---- the rest of prove_fri: challenger, commit-phase leaf view, final polynomial, schedule, and their composition
     def challenger(self):
