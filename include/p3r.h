@@ -917,6 +917,70 @@ int p3r_lookup_multiplicities_dmat(p3r_ctx* ctx,
                                    p3r_dmat** out,                                      /* fresh h_T x n_terms_T, the caller frees */
                                    p3r_lookup_imbalance* missing, size_t cap, uint64_t* n_missing_out);
 
+/* ---- derived trace columns: witness programs store values of resident traces as columns ----
+ *
+ * Functions and enumerators are only added: P3R_ABI_VERSION stays as it is, and no entry above changes what it accepts,
+ * refuses or says.
+ *
+ * The limbs a range check looks up, the column 0 .. h-1 that IS the range table, the inverse witness of an is-zero gadget,
+ * products, selector columns, the flattened key of a bus: row-local functions of columns that already lie in device
+ * memory, and part of the MAIN trace, so they must exist before the trace commitment.  p3r_witness_program_dmat derives
+ * them where the traces lie, as p3r_lookup_multiplicities_dmat derives the multiplicity column.
+ *
+ * A witness program is a p3r_air_insn array in the SSA form above - the same typing, operand rules and canonical words,
+ * the same liveness against P3R_AIR_MAX_LIVE.  It takes every value op of a constraint program, and the three selectors
+ * with the values p3r_check_program_dmat gives them on the trace domain (is_first_row = [r == 0], is_last_row =
+ * [r == h - 1], is_transition = [r != h - 1]).  Four ops are its own; they stay unknown ops to every entry above:
+ *
+ *   P3R_AIR_INV                a = value id                               the operand's type: its inverse, and 0 for 0 -
+ *                                                                         try_inverse().unwrap_or_default(), the witness of
+ *                                                                         an is-zero gadget; defined behaviour, not an error
+ *   P3R_AIR_BITS               a = value id (base only), b = lo | n << 8  base: bits [lo, lo + n) of the CANONICAL word of
+ *                                                                         the operand; n >= 1 and lo + n <= 31
+ *   P3R_AIR_ROW                none                                       base: the row index r
+ *   P3R_AIR_STORE              a = value id, b = output column            none (it may not be referenced): a base value
+ *                                                                         fills column b, an extension value the columns
+ *                                                                         b .. b + DC, coefficient k in column b + k - the
+ *                                                                         flattening P3R_AIR_LOCAL_EXT reads
+ *
+ * ASSERT_ZERO, LOOKUP and LOOKUP_END are refused in a witness program.
+ *
+ * Semantics.  The inputs are TRACES, exactly as p3r_logup_program_dmat takes them: h rows (a power of two), natural
+ * order, one common height, not LDEs.  Row r is the current row; NEXT reads row (r + 1) mod h of an INPUT (h = 1: the row
+ * itself).  n_mats == 0 is legal - a table built from ROW alone has no input - and then `height` gives h; otherwise
+ * `height` must be 0 or the matrices' height.  *out is one fresh h x W matrix the caller frees, W one past the highest
+ * stored column, rows in natural order: it goes to p3r_coset_lde_dmat, p3r_check_program_dmat and the lookup entries as it
+ * is.  The call only enqueues on the context's stream, like p3r_quotient_program_dmat; nothing is read back.
+ *
+ * Out of scope: recurrences - a column that reads its own previous row - and prefix sums.  A program reads inputs only,
+ * never what it stores.  Such columns stay with the caller, or with the running sum of p3r_logup_program_dmat.
+ *
+ * p3r_witness_program_info (host only, no context, as p3r_air_program_info) validates a program against the matrix widths
+ * and reports n_stores, n_out_columns (W), n_inversions and peak_live.  P3R_OK, or the refusal p3r_witness_program_dmat
+ * would give for the program (message: p3r_last_error(NULL)).
+ *
+ * Refusals of p3r_witness_program_dmat, with a message, before anything is allocated or launched; the context stays
+ * usable.  P3R_EINVAL: everything p3r_logup_program_dmat refuses about operands, ops, matrices, columns, indices, heights
+ * and non-canonical words; a sink op of another seam; BITS on an extension value, or with n == 0 or lo + n > 31; INV, BITS
+ * or STORE with an operand that is not an earlier value or is a STORE; no STORE; an output column stored twice, or an
+ * extension store that overlaps another store; an output column below W that nothing stores; n_mats == 0 with a height
+ * that is 0, not a power of two or above 2^TWO_ADICITY; a height that is not the matrices'; a NULL out.  P3R_EUNSUPPORTED:
+ * more live values than P3R_AIR_MAX_LIVE (STORE takes no slot); zk contexts.  The interpreter is the one of the seams
+ * above with a fifth sink: a lane stores its row's word of a column, consecutive lanes consecutive words, no atomics. */
+enum { P3R_AIR_INV = 23, P3R_AIR_BITS = 24, P3R_AIR_ROW = 25, P3R_AIR_STORE = 26 };   /* witness programs only */
+typedef struct p3r_witness_info {
+  uint32_t n_stores;
+  uint32_t n_out_columns;   /* W: the width of the matrix p3r_witness_program_dmat returns */
+  uint32_t n_inversions;    /* INV instructions: one field inversion per row each */
+  uint32_t peak_live;
+} p3r_witness_info;
+int p3r_witness_program_info(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
+                             p3r_witness_info* out);
+int p3r_witness_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,
+                             size_t height, const uint32_t* public_values, size_t n_public,
+                             const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
+                             p3r_dmat** out);
+
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *
  * p3r_prep_create  == ProverData::from_airs_and_degrees + CircuitProverData::new as called by

@@ -278,6 +278,13 @@ class AirProgram {
   // (one is opened if none is open); end_lookup_column closes it
   void lookup(Value multiplicity, Value denominator) { emit(P3R_AIR_LOOKUP, multiplicity.id, denominator.id); }
   void end_lookup_column() { emit(P3R_AIR_LOOKUP_END); }
+  // a witness program (witness_columns): inv is the inverse and 0 for 0, bits the bits [lo, lo + n) of a base value's
+  // canonical word, row the row index; store is the sink - a base value fills output column `column`, an extension value
+  // the columns column .. column + DC
+  Value inv(Value v) { return emit(P3R_AIR_INV, v.id); }
+  Value bits(Value v, uint32_t lo, uint32_t n) { return emit(P3R_AIR_BITS, v.id, lo | n << 8); }
+  Value row() { return emit(P3R_AIR_ROW); }
+  void store(Value v, uint32_t column) { emit(P3R_AIR_STORE, v.id, column); }
   Value emit(uint32_t op, uint32_t a = 0, uint32_t b = 0) {
     insns_.push_back(p3r_air_insn{op, a, b});
     return Value{this, (uint32_t)insns_.size() - 1};
@@ -294,6 +301,13 @@ class AirProgram {
   p3r_lookup_info lookup_info(const Context& ctx, const std::vector<size_t>& widths) const {
     p3r_lookup_info out{};
     const int rc = p3r_lookup_program_info(&ctx.config(), insns_.data(), insns_.size(), widths.data(), widths.size(), &out);
+    if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
+    return out;
+  }
+  // of a witness program: n_stores, n_out_columns, n_inversions, peak_live - or the refusal
+  p3r_witness_info witness_info(const Context& ctx, const std::vector<size_t>& widths) const {
+    p3r_witness_info out{};
+    const int rc = p3r_witness_program_info(&ctx.config(), insns_.data(), insns_.size(), widths.data(), widths.size(), &out);
     if (rc != P3R_OK) throw Error(rc, p3r_last_error(nullptr));
     return out;
   }
@@ -431,6 +445,20 @@ inline LookupMultiplicities lookup_multiplicities(const Context& ctx, const Look
   ctx.check(p3r_lookup_multiplicities_dmat(ctx.raw(), &tab, qs.data(), qs.size(), challenges.data(), challenges.size() / dc, &out.column,
                                            out.missing.data(), cap, &out.n_missing));
   out.missing.resize((size_t)std::min<uint64_t>(cap, out.n_missing));
+  return out;
+}
+
+// Derived columns of a trace, built on the device (p3r.h: p3r_witness_program_dmat): `program` is a witness program
+// (AirProgram::store as its sink, inv / bits / row among its value ops), `mats` the TRACES it reads (one height h,
+// natural order, not LDEs; none: `height` rows).  Returns the h x W matrix of the stored columns, which the caller frees:
+// a trace like any other.  Only enqueues.
+inline p3r_dmat* witness_columns(const Context& ctx, const AirProgram& program, const std::vector<const p3r_dmat*>& mats, size_t height = 0,
+                                 const std::vector<uint32_t>& public_values = {}, const std::vector<uint32_t>& challenges = {}) {
+  const size_t dc = ctx.config().challenge_degree ? ctx.config().challenge_degree : 4;
+  if (challenges.size() % dc) throw Error(P3R_EINVAL, "challenges are DC words each");
+  p3r_dmat* out = nullptr;
+  ctx.check(p3r_witness_program_dmat(ctx.raw(), program.insns().data(), program.insns().size(), mats.data(), mats.size(), height,
+                                     public_values.data(), public_values.size(), challenges.data(), challenges.size() / dc, &out));
   return out;
 }
 

@@ -22,6 +22,8 @@ P3R_EXT_ZK_DETERMINISTIC = 4        # ZK key taken as it is, p3r_zk_set_nonce al
  P3R_AIR_ASSERT_ZERO) = (0, 1) + tuple(range(8, 21))
 # the sinks of a lookup program (p3r_logup_program_dmat); unknown ops to the constraint-program entries
 P3R_AIR_LOOKUP, P3R_AIR_LOOKUP_END = 21, 22
+# the ops of a witness program (p3r_witness_program_dmat); unknown ops to every other entry
+P3R_AIR_INV, P3R_AIR_BITS, P3R_AIR_ROW, P3R_AIR_STORE = 23, 24, 25, 26
 P3R_AIR_MAX_LIVE = 48
 P3R_LOOKUP_CHECK_MAX_RECORDS = 1 << 28    # p3r_lookup_check_dmat: term slots (rows x terms over the instances) of one call
 P3R_EINVAL, P3R_EUNSUPPORTED, P3R_EVERIFY = -1, -5, -7   # P3R_EVERIFY: a well-formed proof the FRI verifier seam rejects
@@ -98,6 +100,10 @@ class P3rAirInfo(C.Structure):
 class P3rLookupInfo(C.Structure):
     _fields_ = [("n_terms", C.c_uint32), ("n_columns", C.c_uint32), ("max_terms_per_column", C.c_uint32),
                 ("max_constraint_degree", C.c_uint32), ("peak_live", C.c_uint32)]
+
+
+class P3rWitnessInfo(C.Structure):   # p3r_witness_program_info
+    _fields_ = [("n_stores", C.c_uint32), ("n_out_columns", C.c_uint32), ("n_inversions", C.c_uint32), ("peak_live", C.c_uint32)]
 
 
 class P3rCheckReport(C.Structure):   # p3r_check_program_dmat
@@ -301,6 +307,11 @@ SIGNATURES = {
     "p3r_lookup_multiplicities_dmat": (C.c_int, [vp, C.POINTER(P3rLookupInstance), C.POINTER(P3rLookupInstance), C.c_size_t, u32p,
                                                  C.c_size_t, C.POINTER(vp), C.POINTER(P3rLookupImbalance), C.c_size_t,
                                                  C.POINTER(C.c_uint64)]),
+    # derived trace columns: a witness program's stored values as a new resident trace
+    "p3r_witness_program_info": (C.c_int, [C.POINTER(P3rConfig), C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
+                                           C.POINTER(P3rWitnessInfo)]),
+    "p3r_witness_program_dmat": (C.c_int, [vp, C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(vp), C.c_size_t, C.c_size_t, u32p, C.c_size_t,
+                                           u32p, C.c_size_t, C.POINTER(vp)]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

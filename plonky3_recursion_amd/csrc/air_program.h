@@ -1,11 +1,14 @@
 // The host half of the constraint-program seam (p3r_air_program_info, p3r_quotient_program_dmat; include/p3r.h) and of
-// the lookup-program seam (p3r_lookup_program_info, p3r_logup_program_dmat): what is decided about a caller's p3r_air_insn
-// program before anything touches the device.  Host only, no HIP and no context: tu_air.hip turns a plan into a launch,
-// tests/air_program_host_main.cpp and tests/lookup_program_host_main.cpp walk it with g++ alone.
+// the lookup-program seam (p3r_lookup_program_info, p3r_logup_program_dmat) and of the witness seam
+// (p3r_witness_program_info, p3r_witness_program_dmat): what is decided about a caller's p3r_air_insn program before
+// anything touches the device.  Host only, no HIP and no context: tu_air.hip turns a plan into a launch,
+// tests/air_program_host_main.cpp, tests/lookup_program_host_main.cpp and tests/witness_program_host_main.cpp walk it with
+// g++ alone.
 //
 //   air_plan      validation, typing (base / extension), the degree walk, liveness and the assignment of values to slots;
 //                 in AIR_MODE_LOOKUP the sinks are P3R_AIR_LOOKUP / P3R_AIR_LOOKUP_END instead of ASSERT_ZERO, and the
-//                 degree reported is that of each auxiliary column's constraint
+//                 degree reported is that of each auxiliary column's constraint; in AIR_MODE_WITNESS the sink is
+//                 P3R_AIR_STORE, the ops INV / BITS / ROW are known, and the output columns must be stored exactly once
 //   air_compile   the instruction stream the interpreter reads: operands as LDS word offsets, ops specialised by the
 //                 operand types, constants and public values in Montgomery form, challenges in a side table
 //   air_domain    the per-chunk constants of the quotient domain: x^h - 1 and its inverse on each of the 2^q cosets
@@ -37,24 +40,30 @@ constexpr size_t kAirMaxLdsBytes = (size_t)P3R_AIR_MAX_LIVE * (kMaxAirDC + 1) * 
 constexpr uint32_t kAirNoSlot = 0xffffffffu;
 constexpr size_t kAirUnknownCount = ~size_t(0);   // n_public / n_challenges of p3r_air_program_info: not checked
 
-// What a program's sinks are: the constraints of the quotient seam, or the terms and columns of the lookup seam.
-enum AirMode { AIR_MODE_CONSTRAINTS, AIR_MODE_LOOKUP };
+// What a program's sinks are: the constraints of the quotient seam, the terms and columns of the lookup seam, or the
+// stored columns of the witness seam.
+enum AirMode { AIR_MODE_CONSTRAINTS, AIR_MODE_LOOKUP, AIR_MODE_WITNESS };
 
 inline bool air_op_is_binary(uint32_t op) { return op == P3R_AIR_ADD || op == P3R_AIR_SUB || op == P3R_AIR_MUL; }
 inline bool air_op_known(uint32_t op, AirMode mode = AIR_MODE_CONSTRAINTS) {
   return op == P3R_AIR_CONST || op == P3R_AIR_PUBLIC || (op >= P3R_AIR_CHALLENGE && op <= P3R_AIR_ASSERT_ZERO) ||
-         (mode == AIR_MODE_LOOKUP && (op == P3R_AIR_LOOKUP || op == P3R_AIR_LOOKUP_END));
+         (mode == AIR_MODE_LOOKUP && (op == P3R_AIR_LOOKUP || op == P3R_AIR_LOOKUP_END)) ||
+         (mode == AIR_MODE_WITNESS && op >= P3R_AIR_LOOKUP && op <= P3R_AIR_STORE);   // the other seams' sinks: refused by name
 }
 // an instruction that defines no value
-inline bool air_op_is_sink(uint32_t op) { return op == P3R_AIR_ASSERT_ZERO || op == P3R_AIR_LOOKUP || op == P3R_AIR_LOOKUP_END; }
+inline bool air_op_is_sink(uint32_t op) {
+  return op == P3R_AIR_ASSERT_ZERO || op == P3R_AIR_LOOKUP || op == P3R_AIR_LOOKUP_END || op == P3R_AIR_STORE;
+}
 // number of value operands
 inline int air_op_operands(uint32_t op) {
-  return air_op_is_binary(op) || op == P3R_AIR_LOOKUP ? 2 : (op == P3R_AIR_NEG || op == P3R_AIR_ASSERT_ZERO) ? 1 : 0;
+  return air_op_is_binary(op) || op == P3R_AIR_LOOKUP ? 2
+         : (op == P3R_AIR_NEG || op == P3R_AIR_ASSERT_ZERO || op == P3R_AIR_INV || op == P3R_AIR_BITS || op == P3R_AIR_STORE) ? 1 : 0;
 }
 
 struct AirPlan {
   p3r_air_info info{};
   p3r_lookup_info lookup{};         // AIR_MODE_LOOKUP
+  p3r_witness_info witness{};       // AIR_MODE_WITNESS
   std::vector<uint32_t> column_degree;   // AIR_MODE_LOOKUP: the degree of each closed column's constraint
   std::vector<uint8_t> is_ext;      // per value
   std::vector<uint32_t> slot;       // per value: its slot in the region of its kind; kAirNoSlot for a sink
@@ -92,10 +101,16 @@ inline int air_trace_log_height(size_t h, int two_adicity) {
 // has the degree max(1 + sum_k deg d_k, max_k(deg m_k + sum_{l != k} deg d_l)): kept per open column as the two running
 // figures den_deg = sum_k deg d_k and num_deg = max_k(deg m_k + sum_{l != k} deg d_l) over the terms met so far.  A lookup
 // program has no constraints of its own and no selectors.
+//
+// AIR_MODE_WITNESS: a STORE (a = value, b = output column) fills one column with a base value and DC with an extension
+// value.  The columns 0 .. W - 1, W one past the highest stored, must each be stored exactly once; a witness program has no
+// constraints and no lookups, and degrees mean nothing to it.
 inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths, size_t n_mats, int dc, uint32_t p,
                         size_t n_public, size_t n_challenges, uint32_t max_live, AirMode mode = AIR_MODE_CONSTRAINTS) {
-  const bool lookup = mode == AIR_MODE_LOOKUP;
-  if (n == 0 || !prog) fail(P3R_EINVAL, lookup ? "the program has no LOOKUP (it is empty)" : "the program has no ASSERT_ZERO (it is empty)");
+  const bool lookup = mode == AIR_MODE_LOOKUP, witness = mode == AIR_MODE_WITNESS;
+  if (n == 0 || !prog)
+    fail(P3R_EINVAL, witness ? "the program has no STORE (it is empty)"
+                     : lookup ? "the program has no LOOKUP (it is empty)" : "the program has no ASSERT_ZERO (it is empty)");
   if (n > 0x7fffffffu) fail(P3R_EINVAL, "the program is too long");
   if (n_mats && !widths) fail(P3R_EINVAL, "widths is NULL");
   constexpr uint64_t kDegCap = uint64_t(1) << 40;   // saturates: a chain of squarings must not wrap
@@ -109,6 +124,8 @@ inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths
   bool column_open = false;
   uint64_t den_deg = 0, num_deg = 0;      // of the open column
   uint32_t column_terms = 0;
+  struct Store { uint64_t first, end; size_t insn; };   // output columns [first, end) of a STORE
+  std::vector<Store> stores;
   for (size_t i = 0; i < n; ++i) {
     const p3r_air_insn& in = prog[i];
     pl.last_use[i] = (uint32_t)i;
@@ -116,12 +133,16 @@ inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths
     if (lookup && in.op == P3R_AIR_ASSERT_ZERO) fail(P3R_EINVAL, "instruction %zu: ASSERT_ZERO in a lookup program, which has no constraints", i);
     if (lookup && (in.op == P3R_AIR_IS_FIRST_ROW || in.op == P3R_AIR_IS_LAST_ROW || in.op == P3R_AIR_IS_TRANSITION))
       fail(P3R_EINVAL, "instruction %zu: a selector (op %u) in a lookup program: selectors have no value on the trace domain here", i, in.op);
+    if (witness && in.op == P3R_AIR_ASSERT_ZERO) fail(P3R_EINVAL, "instruction %zu: ASSERT_ZERO in a witness program, which has no constraints", i);
+    if (witness && (in.op == P3R_AIR_LOOKUP || in.op == P3R_AIR_LOOKUP_END))
+      fail(P3R_EINVAL, "instruction %zu: %s in a witness program, which has no lookups", i, in.op == P3R_AIR_LOOKUP ? "LOOKUP" : "LOOKUP_END");
     const int n_ops = air_op_operands(in.op);
     const uint32_t ops[2] = {in.a, in.b};
     for (int k = 0; k < n_ops; ++k) {
       if (ops[k] >= i) fail(P3R_EINVAL, "instruction %zu: operand %u is not an earlier value", i, ops[k]);
       if (is_assert[ops[k]])
-        fail(P3R_EINVAL, "instruction %zu: operand %u is %s, which has no value", i, ops[k], lookup ? "a LOOKUP or LOOKUP_END" : "an ASSERT_ZERO");
+        fail(P3R_EINVAL, "instruction %zu: operand %u is %s, which has no value", i, ops[k],
+             witness ? "a STORE" : lookup ? "a LOOKUP or LOOKUP_END" : "an ASSERT_ZERO");
       pl.last_use[ops[k]] = (uint32_t)i;
     }
     switch (in.op) {
@@ -192,9 +213,44 @@ inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths
         ++pl.lookup.n_columns;
         break;
       }
+      case P3R_AIR_INV:
+        pl.is_ext[i] = pl.is_ext[in.a];
+        ++pl.witness.n_inversions;
+        break;
+      case P3R_AIR_BITS: {
+        const uint32_t lo = in.b & 0xffu, bits = in.b >> 8;
+        if (pl.is_ext[in.a]) fail(P3R_EINVAL, "instruction %zu: BITS of an extension value: only a base value has a canonical word", i);
+        if (bits == 0 || (uint64_t)lo + bits > 31)
+          fail(P3R_EINVAL, "instruction %zu: BITS [%u, %u + %u): at least one bit, and none above bit 30 of the canonical word", i, lo, lo, bits);
+        break;
+      }
+      case P3R_AIR_ROW:
+        break;
+      case P3R_AIR_STORE: {
+        is_assert[i] = 1;
+        const uint64_t end = (uint64_t)in.b + (pl.is_ext[in.a] ? (uint64_t)dc : 1);
+        if (end > 0x7fffffffu) fail(P3R_EINVAL, "instruction %zu: output column %u: too many output columns", i, in.b);
+        stores.push_back({in.b, end, i});
+        ++pl.witness.n_stores;
+        break;
+      }
     }
   }
-  if (lookup) {
+  if (witness) {
+    if (stores.empty()) fail(P3R_EINVAL, "the program has no STORE");
+    std::sort(stores.begin(), stores.end(), [](const Store& x, const Store& y) { return x.first != y.first ? x.first < y.first : x.insn < y.insn; });
+    uint64_t covered = 0;   // the columns below are stored exactly once
+    for (const Store& st : stores) {
+      if (st.first < covered)
+        fail(P3R_EINVAL, "instruction %zu: output column %llu is stored twice (the columns of an extension value are %d)", st.insn,
+             (unsigned long long)st.first, dc);
+      if (st.first > covered)
+        fail(P3R_EINVAL, "output column %llu is stored by no instruction (the program stores up to column %llu)", (unsigned long long)covered,
+             (unsigned long long)stores.back().end - 1);
+      covered = st.end;
+    }
+    pl.witness.n_out_columns = (uint32_t)covered;
+  } else if (lookup) {
     if (pl.lookup.n_terms == 0) fail(P3R_EINVAL, "the program has no LOOKUP");
     if (column_open) fail(P3R_EINVAL, "the program ends with a column still open (a LOOKUP_END is missing)");
     pl.lookup.max_constraint_degree = (uint32_t)std::min<uint64_t>(max_deg, 0xffffffffu);
@@ -229,7 +285,7 @@ inline AirPlan air_plan(const p3r_air_insn* prog, size_t n, const size_t* widths
     peak = std::max(peak, ++live);
     if (pl.last_use[i] == i) release((uint32_t)i);   // never read: its slot is free again at once
   }
-  pl.info.peak_live = pl.lookup.peak_live = peak;
+  pl.info.peak_live = pl.lookup.peak_live = pl.witness.peak_live = peak;
   if (peak > max_live)
     fail(P3R_EUNSUPPORTED, "the program keeps %u values alive at once; P3R_AIR_MAX_LIVE is %u", peak, max_live);
   return pl;
@@ -250,7 +306,13 @@ enum AirDevOp : uint32_t {
   // the lookup seam.  A term m / d joins the open column's fraction num / den: num <- num * d + m * den, den <- den * d
   // (a = m, b = d; _BE: m base, d extension).  COL_END: f = num / den goes to the output columns a * DC .. and to the row's total
   AIR_D_TERM_BB, AIR_D_TERM_BE, AIR_D_TERM_EB, AIR_D_TERM_EE,
-  AIR_D_COL_END
+  AIR_D_COL_END,
+  // the witness seam.  INV: dst <- a^-1, 0 for 0.  BITS: dst <- bits [b & 0xff, (b & 0xff) + (b >> 8)) of a's canonical word.
+  // ROW: dst <- the lane's row.  STORE: a goes to the output column b (_E: the columns b .. b + DC)
+  AIR_D_INV_B, AIR_D_INV_E,
+  AIR_D_BITS,
+  AIR_D_ROW,
+  AIR_D_STORE_B, AIR_D_STORE_E
 };
 struct AirDevInsn {
   uint32_t op, dst, a, b;   // dst and value operands: LDS words of a lane
@@ -303,6 +365,10 @@ inline AirCompiled air_compile(const AirPlan& pl, const p3r_air_insn* prog, size
       case P3R_AIR_ASSERT_ZERO: d.op = ea ? AIR_D_ASSERT_E : AIR_D_ASSERT_B; break;
       case P3R_AIR_LOOKUP: d.op = ea ? (eb ? AIR_D_TERM_EE : AIR_D_TERM_EB) : (eb ? AIR_D_TERM_BE : AIR_D_TERM_BB); break;
       case P3R_AIR_LOOKUP_END: d.op = AIR_D_COL_END; wa = 1 + n_closed++; break;   // output column 0 is the running sum
+      case P3R_AIR_INV: d.op = ea ? AIR_D_INV_E : AIR_D_INV_B; break;
+      case P3R_AIR_BITS: d.op = AIR_D_BITS; wb = in.b; break;
+      case P3R_AIR_ROW: d.op = AIR_D_ROW; break;
+      case P3R_AIR_STORE: d.op = ea ? AIR_D_STORE_E : AIR_D_STORE_B; wb = in.b; break;
     }
     d.a = wa;
     d.b = wb;

@@ -11,9 +11,12 @@
 //                        selectors - per constraint the smallest row in which it does not vanish and the number of such rows.
 //   k_lookup_records     p3r_lookup_check_dmat: the caller's lookups on every row of resident TRACES - every term's
 //                        denominator and multiplicity as canonical words, for the sort and the sums of tu_air.hip.
+//   k_witness_program    p3r_witness_program_dmat: the caller's derived columns on every row of resident TRACES - values
+//                        stored as the columns of a new trace, with the value ops witness generation needs and
+//                        constraints must not have (inverse-or-zero, bit fields of the canonical word, the row index).
 //
-// All four are one interpreter, air_step, with the sinks as a template parameter (QuotProgSink / LogupProgSink /
-// CheckProgSink / RecordSink), as AuxSink / QuotSink share air_interactions for the built-in AIRs.
+// All five are one interpreter, air_step, with the sinks as a template parameter (QuotProgSink / LogupProgSink /
+// CheckProgSink / RecordSink / WitnessSink), as AuxSink / QuotSink share air_interactions for the built-in AIRs.
 //
 // One lane per row: of the quotient domain in storage (bit-reversed) order, of a trace in natural order - either way the
 // read of a column at the current row is one contiguous run per wave; the next row's read is the same run bit-reversal
@@ -386,6 +389,76 @@ __global__ void __launch_bounds__(kAirLanes) k_lookup_records(AirRecordArgs a) {
   sink.mark = as_global(a.mark);
   sink.n_slots = a.n_slots;
   sink.slot = a.base + r * a.n_terms;
+
+  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
+  const gptr<const AirDevInsn> insns = as_global(a.insns);
+  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
+  const gptr<const uint32_t* const> cols = as_global(a.cols);
+  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
+}
+
+// The sinks of a witness program: values become columns.  The selectors are CheckProgSink's 0 / 1.  INV is the field's own
+// inverse - Fp::inv is x^(p-2) and the extension inverses multiply by the inverse of a norm, so 0 comes out as 0 with no
+// guard: the try_inverse().unwrap_or_default() of an is-zero witness.  BITS leaves Montgomery form (one multiplication
+// by 1), shifts and masks the canonical word, and re-enters (one multiplication by R^2); ROW enters the same way (a row is
+// below 2^TWO_ADICITY < p).  A STORE writes word out[col * h + row]: the 64 lanes of the wave write 64 consecutive words of
+// one column, plain vector stores; air_plan has seen to it that every column below the output's width has one writer.
+template <class PP, int DC>
+struct WitnessSink {
+  using F = Fp<PP>;
+  using E = typename Chal<PP, DC>::type;
+  F is_first, is_last, is_transition;
+  gptr<uint32_t> out;
+  size_t h, row;
+  __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
+    switch (in.op) {
+      case AIR_D_FIRST: sl.st(in.dst, is_first); break;
+      case AIR_D_LAST: sl.st(in.dst, is_last); break;
+      case AIR_D_TRANS: sl.st(in.dst, is_transition); break;
+      case AIR_D_INV_B: sl.st(in.dst, sl.ld(in.a).inv()); break;
+      case AIR_D_INV_E: sl.ste(in.dst, sl.lde(in.a).inv()); break;
+      case AIR_D_BITS: {
+        const uint32_t lo = in.b & 0xffu, n = in.b >> 8;   // 1 <= n, lo + n <= 31 (air_plan)
+        sl.st(in.dst, F::from_canonical((sl.ld(in.a).to_canonical() >> lo) & ((1u << n) - 1u)));
+        break;
+      }
+      case AIR_D_ROW: sl.st(in.dst, F::from_canonical((uint32_t)row)); break;
+      case AIR_D_STORE_B: out[(size_t)in.b * h + row] = sl.ld(in.a).v; break;
+      case AIR_D_STORE_E: {
+        const E e = sl.lde(in.a);
+#pragma unroll
+        for (int k = 0; k < DC; ++k) out[((size_t)in.b + k) * h + row] = e.c[k].v;
+        break;
+      }
+      default: break;   // air_compile emits nothing else for a witness program
+    }
+  }
+};
+
+struct AirWitnessArgs {
+  const AirDevInsn* insns;         // n_insns of them
+  const uint32_t* ext_consts;      // Montgomery, DC words per entry
+  const uint32_t* const* cols;     // one pointer per flat input column: h words, natural order
+  uint32_t* out;                   // [W][h]: the stored columns
+  uint32_t n_insns;
+  int log_h;
+};
+
+template <class PP, int DC>
+__global__ void __launch_bounds__(kAirLanes) k_witness_program(AirWitnessArgs a) {
+  using F = Fp<PP>;
+  extern __shared__ uint32_t air_slots[];
+  const size_t h = size_t(1) << a.log_h;
+  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
+  if (r >= h) return;
+  const size_t r_next = (r + 1) & (h - 1);
+  WitnessSink<PP, DC> sink;
+  sink.is_first = r == 0 ? F::one() : F::zero();
+  sink.is_last = r == h - 1 ? F::one() : F::zero();
+  sink.is_transition = r == h - 1 ? F::zero() : F::one();
+  sink.out = as_global(a.out);
+  sink.h = h;
+  sink.row = r;
 
   const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
   const gptr<const AirDevInsn> insns = as_global(a.insns);

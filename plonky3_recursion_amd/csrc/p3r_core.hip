@@ -948,6 +948,36 @@ int p3r_lookup_multiplicities_dmat(p3r_ctx* ctx, const p3r_lookup_instance* tabl
   });
 }
 
+// Derived trace columns as a witness program: air_program.h in its witness mode, tu_air.hip (the launch)
+int p3r_witness_program_info(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
+                             p3r_witness_info* out) {
+  return guard(nullptr, [&] {
+    if (!cfg || !out) fail(P3R_EINVAL, "NULL argument");
+    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
+    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
+      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
+    const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
+    *out = air_plan(prog, n_insns, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p, kAirUnknownCount, kAirUnknownCount,
+                    P3R_AIR_MAX_LIVE, AIR_MODE_WITNESS).witness;
+  });
+}
+int p3r_witness_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const p3r_dmat* const* mats, size_t n_mats,
+                             size_t height, const uint32_t* public_values, size_t n_public, const uint32_t* challenges,
+                             size_t n_challenges, p3r_dmat** out) {
+  return guard(ctx, [&] {
+    if (out) *out = nullptr;
+    if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
+    if (!out) fail(P3R_EINVAL, "out is NULL");
+    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
+    std::vector<const p3r_dmat*> ms(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
+      ms[i] = mats[i];
+    }
+    *out = P3R_FIELD_CALL(ctx, witness_program, ctx, prog, n_insns, ms, height, public_values, n_public, challenges, n_challenges).release();
+  });
+}
+
 int p3r_mmcs_commit_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,
                          uint32_t* cap_out, p3r_tree** tree_out) {
   return guard(ctx, [&] {

@@ -9,6 +9,8 @@
 // and the sums of device_prims.hip.h: the keys of the bus whose multiplicities do not cancel).
 // p3r_lookup_multiplicities_dmat is the same pass (LookupPass) with another end: k_lookup_scatter gives every key's first
 // table slot the sum its queries ask for - the multiplicity column of a table - and reports the keys no table slot offers.
+// The witness seam (p3r_witness_program_dmat) is the interpreter once more, in its witness mode (k_witness_program): the
+// values a program stores become the columns of a new trace.  One launch; the call only enqueues.
 #include <algorithm>
 
 #include "device_prims.hip.h"
@@ -126,13 +128,16 @@ struct TraceProgram {
   size_t h = 0, n_cols = 0, lds = 0;
   int log_h = 0;
 };
+// `height`: the witness seam's, which takes a program with no input matrix and then needs it; 0 with matrices: theirs.
 template <class PP, int DC>
 TraceProgram trace_program(const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats, const uint32_t* publics,
-                           size_t n_public, const uint32_t* challenges, size_t n_challenges, AirMode mode) {
+                           size_t n_public, const uint32_t* challenges, size_t n_challenges, AirMode mode, size_t height = 0) {
   TraceProgram tp;
-  if (mats.empty()) fail(P3R_EINVAL, "n_mats == 0: no trace to evaluate the program on");
+  if (mats.empty() && mode != AIR_MODE_WITNESS) fail(P3R_EINVAL, "n_mats == 0: no trace to evaluate the program on");
   if ((n_public && !publics) || (n_challenges && !challenges)) fail(P3R_EINVAL, "public_values or challenges is NULL");
-  const size_t h = tp.h = mats[0]->h;
+  const size_t h = tp.h = mats.empty() ? height : mats[0]->h;
+  if (!mats.empty() && height && height != h)
+    fail(P3R_EINVAL, "height (%zu) is not the matrices' (%zu): pass 0, or the height of the traces", height, h);
   tp.log_h = air_trace_log_height(h, PP::TWO_ADICITY);   // a power of two within the field's two-adicity
   tp.widths.resize(mats.size());
   for (size_t m = 0; m < mats.size(); ++m) {
@@ -261,6 +266,45 @@ std::unique_ptr<p3r_dmat> logup_program_dc(p3r_ctx* ctx, const p3r_air_insn* pro
   P3R_HIP(fetch_small(ctx, d_answer, 1 + DC, answer));   // waits for the stream
   if (answer[0] != 0xffffffffu) fail(P3R_EINVAL, "zero denominator in row %u: the fraction of an auxiliary column is not defined there", answer[0]);
   for (int k = 0; k < DC; ++k) sum_out[k] = F::raw(answer[1 + k]).to_canonical();
+  return out;
+}
+
+// The witness seam (p3r_witness_program_dmat): the values a witness program stores, as the columns of a fresh trace.  One
+// launch of k_witness_program; nothing is read back and the call does not wait.
+template <class PP, int DC>
+std::unique_ptr<p3r_dmat> witness_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
+                                             size_t height, const uint32_t* publics, size_t n_public, const uint32_t* challenges,
+                                             size_t n_challenges) {
+  // ---- everything that is refused, before anything is allocated or launched
+  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the witness seam does not serve zk contexts (their traces are randomised and their domains doubled)");
+  const TraceProgram tp = trace_program<PP, DC>(prog, n_insns, mats, publics, n_public, challenges, n_challenges, AIR_MODE_WITNESS, height);
+  const size_t W = tp.plan.witness.n_out_columns;
+
+  // ---- the launch
+  const AirCompiled code = air_compile<PP>(tp.plan, prog, n_insns, tp.widths.data(), tp.widths.size(), DC, publics, challenges);
+  std::unique_ptr<p3r_dmat> out = dmat_alloc(tp.h, W);   // [W][h]
+  ProgramBlob blob(0, code, mats, tp.n_cols);
+  blob.upload(ctx);
+  AirWitnessArgs a{};
+  a.insns = blob.insns();
+  a.ext_consts = blob.ext_consts();
+  a.cols = blob.cols();
+  a.out = out->d;
+  a.n_insns = (uint32_t)code.insns.size();
+  a.log_h = tp.log_h;
+  {
+    ProfScope ps(ctx, "witness_program");
+    // rows r < h of every input column are read (with no input matrix the stream has no load); a STORE writes words
+    // col * h + r with col < W - air_plan took W as one past the highest stored column - and r < h: all inside the
+    // allocation above.  Every column below W is stored: nothing of the output stays uninitialised.
+    const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
+    if (tp.lds > 48 * 1024)
+      P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_witness_program<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)kAirMaxLdsBytes));
+    hipLaunchKernelGGL((k_witness_program<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, ctx->stream, a);
+  }
+  P3R_HIP(hipGetLastError());
+  // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
   return out;
 }
 
@@ -742,6 +786,17 @@ std::unique_ptr<p3r_dmat> lookup_multiplicities(p3r_ctx* ctx, const std::vector<
   return lookup_multiplicities_dc<PP, 4>(ctx, insts, challenges, n_challenges, missing, cap, n_missing_out);
 }
 
+template <class PP>
+std::unique_ptr<p3r_dmat> witness_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
+                                          size_t height, const uint32_t* publics, size_t n_public, const uint32_t* challenges,
+                                          size_t n_challenges) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>) return witness_program_dc<PP, 5>(ctx, prog, n_insns, mats, height, publics, n_public, challenges, n_challenges);
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  return witness_program_dc<PP, 4>(ctx, prog, n_insns, mats, height, publics, n_public, challenges, n_challenges);
+}
+
 #define P3R_AIR_INSTANCE(PP)                                                                                                     \
   template std::vector<std::unique_ptr<p3r_dmat>> quotient_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t,                    \
                                                                        const std::vector<const p3r_dmat*>&, uint32_t, uint32_t, \
@@ -766,5 +821,11 @@ P3R_LOGUP_INSTANCE(BabyBearParams)
 P3R_CHECK_INSTANCE(KoalaBearParams)
 P3R_CHECK_INSTANCE(BabyBearParams)
 #undef P3R_CHECK_INSTANCE
+#define P3R_WITNESS_INSTANCE(PP)                                                                                                       \
+  template std::unique_ptr<p3r_dmat> witness_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&,   \
+                                                         size_t, const uint32_t*, size_t, const uint32_t*, size_t);
+P3R_WITNESS_INSTANCE(KoalaBearParams)
+P3R_WITNESS_INSTANCE(BabyBearParams)
+#undef P3R_WITNESS_INSTANCE
 
 }  // namespace p3r

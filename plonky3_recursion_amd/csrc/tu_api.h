@@ -160,6 +160,15 @@ template <class PP>
 std::unique_ptr<p3r_dmat> lookup_multiplicities(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges,
                                                 size_t n_challenges, p3r_lookup_imbalance* missing, size_t cap, uint64_t* n_missing_out);
 
+// Derived columns of a caller's trace (tu_air.hip): the witness program `prog` (p3r_air_insn with P3R_AIR_STORE as its sink
+// and INV / BITS / ROW among its value ops) evaluated on every row of the traces `mats` (one height h, natural order; none:
+// `height` rows).  Returns the fresh h x W matrix of the stored columns.  Everything that is refused is refused before
+// anything is allocated or launched (include/p3r.h lists it); only enqueues.
+template <class PP>
+std::unique_ptr<p3r_dmat> witness_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
+                                          size_t height, const uint32_t* publics, size_t n_public, const uint32_t* challenges,
+                                          size_t n_challenges);
+
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>
 void launch_logup_aux(p3r_ctx* ctx, unsigned blocks, const LogupJob* d_jobs, int n_jobs, const LookupChT<DC>& lc);

@@ -499,6 +499,27 @@ class AirBuilder:
         """Closes the open auxiliary column of a lookup program."""
         self._emit(_lib.P3R_AIR_LOOKUP_END)
 
+    # ---- a witness program (Context.witness_device): values become the columns of a new trace
+    def _value(self, v):
+        return v if isinstance(v, AirValue) else self.const(int(v) % self.p)
+
+    def inv(self, value):
+        """The inverse of a base or extension value, and 0 for 0: the witness of an is-zero gadget."""
+        return self._emit(_lib.P3R_AIR_INV, self._value(value).idx)
+
+    def bits(self, value, lo, n):
+        """Bits [lo, lo + n) of the canonical word of a base value (n >= 1, lo + n <= 31)."""
+        return self._emit(_lib.P3R_AIR_BITS, self._value(value).idx, int(lo) | int(n) << 8)
+
+    def row(self):
+        """The row index, as a base value."""
+        return self._emit(_lib.P3R_AIR_ROW)
+
+    def store(self, value, column):
+        """A witness program's sink: a base value fills output column `column`, an extension value the columns
+        column .. column + DC (coefficient k in column + k, the flattening local_ext reads).  Python ints become constants."""
+        self._emit(_lib.P3R_AIR_STORE, self._value(value).idx, column)
+
     def program(self):
         """The instructions as an (n, 3) uint32 array of (op, a, b)."""
         return np.array(self.insns, dtype=np.uint32).reshape(-1, 3)
@@ -588,6 +609,21 @@ def lookup_program_info(cfg, program, widths):
     if rc != 0:
         raise P3rError(rc, lib.p3r_last_error(None).decode())
     return {k: int(getattr(info, k)) for k, _ in _lib.P3rLookupInfo._fields_}
+
+
+def witness_program_info(cfg, program, widths):
+    """p3r_witness_program_info on the host (no GPU): validates the witness `program` (an AirBuilder or an (n, 3) array of
+    (op, a, b)) against the matrix `widths` (none for a program without inputs) under the field and challenge degree of
+    the p3r_config `cfg`; returns a dict of n_stores, n_out_columns (the width of the matrix witness_device returns),
+    n_inversions and peak_live.  Raises P3rError with the reason when the program is refused."""
+    lib = _lib.load()
+    arr, n = _air_insns(program)
+    ws = (C.c_size_t * max(1, len(widths)))(*[int(w) for w in widths])
+    info = _lib.P3rWitnessInfo()
+    rc = lib.p3r_witness_program_info(C.byref(cfg), arr, n, ws, len(widths), C.byref(info))
+    if rc != 0:
+        raise P3rError(rc, lib.p3r_last_error(None).decode())
+    return {k: int(getattr(info, k)) for k, _ in _lib.P3rWitnessInfo._fields_}
 
 
 class Context:
@@ -973,6 +1009,28 @@ class Context:
         self.check(self.lib.p3r_lookup_multiplicities_dmat(self.h, tab, qs, len(queries), chp, len(ch), C.byref(out), missing, int(cap),
                                                            C.byref(count)))
         return DeviceMatrix(self, self.ptr(out.value)), count.value, _lookup_entries(missing, min(int(cap), count.value), dc)
+
+    # ---- derived trace columns: a witness program's stored values as a new resident trace
+    def witness_program_info(self, program, widths):
+        """witness_program_info under this context's field and challenge degree."""
+        return witness_program_info(self.cfg, program, widths)
+
+    def witness_device(self, program, dmats, height=None, public_values=(), challenges=()):
+        """The columns the witness `program` (an AirBuilder or an (n, 3) array of (op, a, b), with AirBuilder.store as its
+        sink and inv / bits / row among its value ops) derives from the traces `dmats`: one height h, natural row order, not
+        LDEs; `next` reads row (r + 1) mod h of an input.  With no input matrix `height` gives h; otherwise it is None or
+        the matrices' height.  `public_values`: canonical words; `challenges`: (n, DC) canonical words.  Returns a new
+        (h, W) DeviceMatrix, W one past the highest stored column: a trace like any other, for coset_lde_batch_device,
+        check_device and the lookup entries.  Only enqueues; the inputs are left as they are."""
+        dc = self.challenge_degree
+        arr, n = _air_insns(program)
+        mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+        pv, pvp = _u32(np.asarray(public_values, dtype=np.uint32).reshape(-1))
+        ch, chp = _u32(np.asarray(challenges, dtype=np.uint32).reshape(-1, dc))
+        out = C.c_void_p()
+        self.check(self.lib.p3r_witness_program_dmat(self.h, arr, n, mats, len(dmats), 0 if height is None else int(height), pvp, pv.size,
+                                                     chp, len(ch), C.byref(out)))
+        return DeviceMatrix(self, self.ptr(out.value))
 
     # ---- the rest of prove_fri: challenger, commit-phase leaf view, final polynomial, schedule, and their composition
     def challenger(self):
