@@ -981,6 +981,79 @@ int p3r_witness_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_in
                              const uint32_t* challenges /* n_challenges x DC */, size_t n_challenges,
                              p3r_dmat** out);
 
+/* ---- accumulator columns: first-order affine recurrences down the rows of resident traces ----
+ *
+ * Functions and types are only added: P3R_ABI_VERSION stays as it is, no P3R_AIR_* op is added, and no entry above
+ * changes what it accepts, refuses or says.
+ *
+ * The columns the witness section leaves with the caller - a column that reads its own previous row - now go to
+ * p3r_affine_scan_dmat: running sums and cumulative counters, running products (grand-product and memory-permutation
+ * arguments), Horner evaluation down the rows, segmented accumulators that reset on a flag, index accumulators such as
+ * the base-four one of the width-32 Poseidon2 table.  All of them are s[r + 1] = a[r] * s[r] + b[r] with a and b
+ * row-local, and a and b already lie in device memory or come from a witness program: z[r + 1] = z[r] * (gamma - x[r]) /
+ * (gamma - y[r]) takes its factor column from p3r_witness_program_dmat and z from here, with no trip to the host.
+ *
+ * Inputs.  TRACES, exactly as the witness and lookup entries take them: h rows, a power of two up to 2^TWO_ADICITY,
+ * natural order, one common height, not LDEs.
+ *
+ * A recurrence (p3r_recurrence) reads one column for a (mul_mat, mul_col), one for b (add_mat, add_col) and writes one
+ * column of *out (out_col).  With P3R_SCAN_EXT all three are DC consecutive columns, coefficient k in column + k - the
+ * flattening P3R_AIR_LOCAL_EXT reads - and the arithmetic is the challenge field's.  Mixed types are not offered: a
+ * caller lifts a base factor with a witness program.  mul_mat == P3R_SCAN_NONE: a = 1 everywhere (a running sum, and no
+ * multiplication is done); add_mat == P3R_SCAN_NONE: b = 0 everywhere (a running product).  init is s[0]: canonical, DC
+ * words for EXT and word 0 otherwise, the rest zero.
+ *
+ *   s[0] = init,   s[r + 1] = a[r] * s[r] + b[r]   for r in [0, h)
+ *
+ * *out is one fresh h x W matrix the caller frees, W one past the highest written column, rows in natural order: a trace
+ * like any other.  Row r holds s[r], the state ENTERING the row, as column 0 of p3r_logup_program_dmat does; with
+ * P3R_SCAN_INCLUSIVE row r holds s[r + 1].  last_out[5 i .. 5 i + 5) receives s[h] of recurrence i - DC canonical words
+ * (one for a base recurrence), the rest zero: the total a challenger observes, or a last-row constraint compares against.
+ * With last_out == NULL the call only enqueues on the context's stream; otherwise it waits, as p3r_logup_program_dmat
+ * does.
+ *
+ * The constraints the caller then writes for an exclusive column s, with T = last_out:
+ *
+ *   is_first_row  * (s - init)
+ *   is_transition * (s' - a * s - b)
+ *   is_last_row   * (a * s + b - T)
+ *
+ * a = 0 in a row resets the accumulator to b: segmented sums, and the index accumulator above.  Nothing is inverted, and
+ * no error depends on the data.
+ *
+ * Out of scope: coupled or vector-state recurrences (Fibonacci's 2 x 2 step), non-linear recurrences, heights that are
+ * not powers of two.
+ *
+ * p3r_affine_scan_info (host only, no context, as p3r_witness_program_info) validates the descriptors against the matrix
+ * widths and reports W and how many recurrences run as products (no add), sums (no mul) and affine maps.  P3R_OK, or
+ * the refusal p3r_affine_scan_dmat would give for them (message: p3r_last_error(NULL)).
+ *
+ * Refusals of p3r_affine_scan_dmat, with a message, before anything is allocated or launched; the context stays usable.
+ * P3R_EINVAL: n_recs == 0 or above 65535; a NULL recs, out or mats entry; n_mats == 0; matrices of different heights, a
+ * height that is not a power of two or is above 2^TWO_ADICITY; a matrix or column out of range (EXT: column + DC >
+ * width); unknown flag bits; a non-canonical or non-zero-padded init word; two recurrences whose output columns overlap;
+ * an output column below W that nothing writes; a recurrence with neither mul nor add - a constant column, which belongs
+ * in a witness program.  P3R_EUNSUPPORTED: zk contexts.
+ *
+ * Three launches whatever n_recs is (reduce, then scan: per-tile composites of the maps x -> a x + b, one workgroup per
+ * recurrence that carries them across the tiles, then the column); the combine is not commutative and is applied in row
+ * order.  No workgroup waits for another.  Field arithmetic is exact: the result does not depend on the tiling. */
+enum { P3R_SCAN_EXT = 1, P3R_SCAN_INCLUSIVE = 2 };          /* p3r_recurrence.flags */
+#define P3R_SCAN_NONE 0xffffffffu
+typedef struct p3r_recurrence {
+  uint32_t flags;
+  uint32_t mul_mat, mul_col;   /* a: matrix, (first) column; mul_mat == P3R_SCAN_NONE: a = 1 everywhere */
+  uint32_t add_mat, add_col;   /* b: likewise; add_mat == P3R_SCAN_NONE: b = 0 everywhere */
+  uint32_t out_col;            /* (first) column of *out */
+  uint32_t init[5];            /* s[0], canonical, DC words used for EXT, word 0 otherwise, the rest zero */
+} p3r_recurrence;
+typedef struct p3r_scan_info { uint32_t n_out_columns, n_products, n_sums, n_affine; } p3r_scan_info;
+int p3r_affine_scan_info(const p3r_config* cfg, const p3r_recurrence* recs, size_t n_recs,
+                         const size_t* widths, size_t n_mats, p3r_scan_info* out);
+int p3r_affine_scan_dmat(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs,
+                         const p3r_dmat* const* mats, size_t n_mats,
+                         p3r_dmat** out, uint32_t* last_out /* n_recs x 5, HOST, may be NULL */);
+
 /* ---- batch-STARK proving (the chosen drop-in seam) ----
  *
  * p3r_prep_create  == ProverData::from_airs_and_degrees + CircuitProverData::new as called by

@@ -462,6 +462,45 @@ inline p3r_dmat* witness_columns(const Context& ctx, const AirProgram& program, 
   return out;
 }
 
+// Accumulator columns of a trace, built on the device (p3r.h: p3r_affine_scan_dmat): each recurrence is s[0] = init,
+// s[r + 1] = a[r] * s[r] + b[r] with a and b columns of the TRACES `mats` (one height h, natural order, not LDEs).
+// Recurrence::sum / product / affine fill a p3r_recurrence; ext() makes it one over the challenge field (DC consecutive
+// columns each), inclusive() stores s[r + 1] instead of s[r].
+struct Recurrence {
+  p3r_recurrence raw{};
+  static Recurrence affine(uint32_t out_col, uint32_t mul_mat, uint32_t mul_col, uint32_t add_mat, uint32_t add_col,
+                           const std::vector<uint32_t>& init = {0}) {
+    if (init.size() > 5) throw Error(P3R_EINVAL, "init has at most 5 words");
+    Recurrence r;
+    r.raw.mul_mat = mul_mat, r.raw.mul_col = mul_col, r.raw.add_mat = add_mat, r.raw.add_col = add_col, r.raw.out_col = out_col;
+    for (size_t k = 0; k < init.size(); ++k) r.raw.init[k] = init[k];
+    return r;
+  }
+  static Recurrence sum(uint32_t out_col, uint32_t add_mat, uint32_t add_col, const std::vector<uint32_t>& init = {0}) {
+    return affine(out_col, P3R_SCAN_NONE, 0, add_mat, add_col, init);
+  }
+  static Recurrence product(uint32_t out_col, uint32_t mul_mat, uint32_t mul_col, const std::vector<uint32_t>& init = {1}) {
+    return affine(out_col, mul_mat, mul_col, P3R_SCAN_NONE, 0, init);
+  }
+  Recurrence& ext() { raw.flags |= P3R_SCAN_EXT; return *this; }
+  Recurrence& inclusive() { raw.flags |= P3R_SCAN_INCLUSIVE; return *this; }
+};
+struct AffineScan {
+  p3r_dmat* columns = nullptr;   // h x W, the caller frees
+  std::vector<uint32_t> last;    // want_last: 5 words per recurrence, s[h], canonical and zero-padded
+};
+// With want_last the call waits for the stream and fills AffineScan::last; without it it only enqueues.
+inline AffineScan affine_scan(const Context& ctx, const std::vector<Recurrence>& recurrences, const std::vector<const p3r_dmat*>& mats,
+                              bool want_last = false) {
+  std::vector<p3r_recurrence> raws;
+  for (const Recurrence& r : recurrences) raws.push_back(r.raw);
+  AffineScan out;
+  if (want_last) out.last.assign(raws.size() * 5, 0);
+  ctx.check(p3r_affine_scan_dmat(ctx.raw(), raws.data(), raws.size(), mats.data(), mats.size(), &out.columns,
+                                 want_last ? out.last.data() : nullptr));
+  return out;
+}
+
 // DuplexChallenger<F, Perm16, 16, 8> of circuit-prover/src/config.rs over the context's Poseidon2 constants (p3r.h:
 // p3r_challenger).  Host state, except the proof-of-work search of grind.  Words are canonical.
 class DuplexChallenger {

@@ -6,6 +6,7 @@ raises if `libp3r_hip.so` has not been built (no CPU fallback).
 """
 from .device import AirBuilder, Challenger, Context, air_program_info, lookup_program_info, witness_program_info, DeviceMatrix, FriProof, MerkleTree, P3rError, make_config, mmcs_verify, verify_batch  # noqa: F401
 from .device import observe_opened_values, pcs_verify  # noqa: F401
+from .device import Recurrence, affine_scan_info  # noqa: F401
 from .device import air_program_eval, fri_log_arity, fri_verify, fri_verify_transcript, host_challenger  # noqa: F401
 from .prover import (AggregationCircuitFingerprint, AggregationPrepCache, BatchStarkProof, BatchStarkProver, Circuit, CircuitInputs, CircuitPrep,  # noqa: F401
                      CircuitProverData, CircuitRunner, PreparedCircuit, FriRecursionBackend, FriRecursionBackendD5, FriRecursionConfig, NextLayerPrepCache, ProveNextLayerParams,

@@ -24,6 +24,8 @@ P3R_EXT_ZK_DETERMINISTIC = 4        # ZK key taken as it is, p3r_zk_set_nonce al
 P3R_AIR_LOOKUP, P3R_AIR_LOOKUP_END = 21, 22
 # the ops of a witness program (p3r_witness_program_dmat); unknown ops to every other entry
 P3R_AIR_INV, P3R_AIR_BITS, P3R_AIR_ROW, P3R_AIR_STORE = 23, 24, 25, 26
+# p3r_recurrence.flags, and the matrix index that stands for "a = 1" / "b = 0" (p3r_affine_scan_dmat)
+P3R_SCAN_EXT, P3R_SCAN_INCLUSIVE, P3R_SCAN_NONE = 1, 2, 0xFFFFFFFF
 P3R_AIR_MAX_LIVE = 48
 P3R_LOOKUP_CHECK_MAX_RECORDS = 1 << 28    # p3r_lookup_check_dmat: term slots (rows x terms over the instances) of one call
 P3R_EINVAL, P3R_EUNSUPPORTED, P3R_EVERIFY = -1, -5, -7   # P3R_EVERIFY: a well-formed proof the FRI verifier seam rejects
@@ -104,6 +106,15 @@ class P3rLookupInfo(C.Structure):
 
 class P3rWitnessInfo(C.Structure):   # p3r_witness_program_info
     _fields_ = [("n_stores", C.c_uint32), ("n_out_columns", C.c_uint32), ("n_inversions", C.c_uint32), ("peak_live", C.c_uint32)]
+
+
+class P3rRecurrence(C.Structure):   # p3r_affine_scan_dmat: s[r + 1] = a[r] s[r] + b[r]
+    _fields_ = [("flags", C.c_uint32), ("mul_mat", C.c_uint32), ("mul_col", C.c_uint32), ("add_mat", C.c_uint32), ("add_col", C.c_uint32),
+                ("out_col", C.c_uint32), ("init", C.c_uint32 * 5)]
+
+
+class P3rScanInfo(C.Structure):   # p3r_affine_scan_info
+    _fields_ = [("n_out_columns", C.c_uint32), ("n_products", C.c_uint32), ("n_sums", C.c_uint32), ("n_affine", C.c_uint32)]
 
 
 class P3rCheckReport(C.Structure):   # p3r_check_program_dmat
@@ -312,6 +323,10 @@ SIGNATURES = {
                                            C.POINTER(P3rWitnessInfo)]),
     "p3r_witness_program_dmat": (C.c_int, [vp, C.POINTER(P3rAirInsn), C.c_size_t, C.POINTER(vp), C.c_size_t, C.c_size_t, u32p, C.c_size_t,
                                            u32p, C.c_size_t, C.POINTER(vp)]),
+    # accumulator columns: first-order affine recurrences down the rows of resident traces
+    "p3r_affine_scan_info": (C.c_int, [C.POINTER(P3rConfig), C.POINTER(P3rRecurrence), C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
+                                       C.POINTER(P3rScanInfo)]),
+    "p3r_affine_scan_dmat": (C.c_int, [vp, C.POINTER(P3rRecurrence), C.c_size_t, C.POINTER(vp), C.c_size_t, C.POINTER(vp), u32p]),
     "p3r_open_points": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), u32p, u32p]),
     "p3r_mmcs_commit": (C.c_int, [vp, C.POINTER(P3rMatrix), C.c_size_t, u32p, C.POINTER(vp)]),
     "p3r_mmcs_commit_dmat": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, u32p, C.POINTER(vp)]),

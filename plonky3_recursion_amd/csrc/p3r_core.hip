@@ -6,6 +6,7 @@
 #include "kernels_coop.hip.h"
 #include "tu_api.h"
 #include "air_program.h"
+#include "scan_plan.h"
 #include "air_program_eval.h"
 #include "profile.h"
 #include "run_schedule.h"
@@ -975,6 +976,34 @@ int p3r_witness_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_in
       ms[i] = mats[i];
     }
     *out = P3R_FIELD_CALL(ctx, witness_program, ctx, prog, n_insns, ms, height, public_values, n_public, challenges, n_challenges).release();
+  });
+}
+
+// Accumulator columns as affine recurrences: scan_plan.h (the descriptors), tu_air.hip (the launches)
+int p3r_affine_scan_info(const p3r_config* cfg, const p3r_recurrence* recs, size_t n_recs, const size_t* widths, size_t n_mats,
+                         p3r_scan_info* out) {
+  return guard(nullptr, [&] {
+    if (!cfg || !out) fail(P3R_EINVAL, "NULL argument");
+    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
+    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
+      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
+    const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
+    *out = scan_plan(recs, n_recs, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p).info;
+  });
+}
+int p3r_affine_scan_dmat(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs, const p3r_dmat* const* mats, size_t n_mats,
+                         p3r_dmat** out, uint32_t* last_out) {
+  return guard(ctx, [&] {
+    if (out) *out = nullptr;
+    if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
+    if (!out) fail(P3R_EINVAL, "out is NULL");
+    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
+    std::vector<const p3r_dmat*> ms(n_mats);
+    for (size_t i = 0; i < n_mats; ++i) {
+      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
+      ms[i] = mats[i];
+    }
+    *out = P3R_FIELD_CALL(ctx, affine_scan, ctx, recs, n_recs, ms, last_out).release();
   });
 }
 

@@ -11,10 +11,13 @@
 // table slot the sum its queries ask for - the multiplicity column of a table - and reports the keys no table slot offers.
 // The witness seam (p3r_witness_program_dmat) is the interpreter once more, in its witness mode (k_witness_program): the
 // values a program stores become the columns of a new trace.  One launch; the call only enqueues.
+// The recurrence seam (p3r_affine_scan_dmat) is the one entry here that runs no program: the accumulator columns
+// s[r + 1] = a[r] s[r] + b[r] of resident traces, validated by scan_plan.h and scanned by k_affine_scan (kernels_scan.hip.h).
 #include <algorithm>
 
 #include "device_prims.hip.h"
 #include "kernels_air.hip.h"
+#include "kernels_scan.hip.h"
 #include "profile.h"
 #include "tu_api.h"
 
@@ -305,6 +308,70 @@ std::unique_ptr<p3r_dmat> witness_program_dc(p3r_ctx* ctx, const p3r_air_insn* p
   }
   P3R_HIP(hipGetLastError());
   // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
+  return out;
+}
+
+// The recurrence seam (p3r_affine_scan_dmat): the columns s[r + 1] = a[r] s[r] + b[r] of resident traces.  Three launches
+// of k_affine_scan (kernels_scan.hip.h) whatever the number of recurrences; with `last_out` the call waits for the stream
+// and hands back s[h] of each, otherwise it only enqueues.
+template <class PP, int DC>
+std::unique_ptr<p3r_dmat> affine_scan_dc(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs, const std::vector<const p3r_dmat*>& mats,
+                                         uint32_t* last_out) {
+  using F = Fp<PP>;
+  // ---- everything that is refused, before anything is allocated or launched
+  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the recurrence seam does not serve zk contexts (their traces are randomised and their domains doubled)");
+  std::vector<size_t> widths(mats.size());
+  for (size_t m = 0; m < mats.size(); ++m) widths[m] = mats[m]->w;
+  const ScanPlan plan = scan_plan(recs, n_recs, widths.data(), widths.size(), DC, PP::P);   // n_mats == 0 is refused here
+  const size_t h = mats[0]->h;
+  scan_log_height(h, PP::TWO_ADICITY);
+  for (size_t m = 0; m < mats.size(); ++m)
+    if (mats[m]->h != h) fail(P3R_EINVAL, "matrix %zu has %zu rows, matrix 0 has %zu: the traces of one table share a height", m, mats[m]->h, h);
+  const size_t W = plan.info.n_out_columns, n_tiles = scan_tiles(h);
+
+  // ---- the launches
+  std::unique_ptr<p3r_dmat> out = dmat_alloc(h, W);   // [W][h]
+  const size_t agg_words = (size_t)3 * DC * n_tiles;  // per recurrence: the tiles' A, B and entering state
+  DevBuf agg(n_recs * agg_words), d_last(n_recs * kAffMaxDC);
+  std::vector<AffRec> host(n_recs);
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  for (size_t i = 0; i < n_recs; ++i) {
+    const p3r_recurrence& r = recs[i];
+    AffRec& d = host[i];
+    d = AffRec{};
+    d.form = plan.form[i];
+    if (d.form & AFF_MUL) d.a = mats[r.mul_mat]->d + (size_t)r.mul_col * h;
+    if (d.form & AFF_ADD) d.b = mats[r.add_mat]->d + (size_t)r.add_col * h;
+    d.out = out->d + (size_t)r.out_col * h;
+    d.agg = agg.p + i * agg_words;
+    d.last = d_last.p + i * kAffMaxDC;
+    for (int k = 0; k < ((d.form & AFF_EXT) ? DC : 1); ++k) d.init[k] = F::from_canonical(r.init[k]).v;
+    d.inclusive = (r.flags & P3R_SCAN_INCLUSIVE) ? 1u : 0u;
+    d.vec = h % kAffItems == 0 && aligned(d.a) && aligned(d.b) && aligned(d.out);
+  }
+  DevBuf d_recs((n_recs * sizeof(AffRec) + 3) / 4);
+  P3R_HIP(ctx->stage.upload(ctx->stream, d_recs.p, host.data(), n_recs * sizeof(AffRec)));
+  {
+    ProfScope ps(ctx, "affine_scan");
+    // Rows i < h of columns [col, col + D) of the inputs are read and of the output written, col + D within the matrix's
+    // width (scan_plan); a 16-byte access covers rows [i, i + 4) with i + 4 <= h.  Words word * n_tiles + tile with
+    // word < 3 D <= 3 DC and tile < n_tiles of a recurrence's scratch and the kAffMaxDC words of its total are written:
+    // all inside the allocations above.  Every column below W has one writer: nothing of the output stays uninitialised.
+    const auto* dr = reinterpret_cast<const AffRec*>(d_recs.p);
+    const dim3 tiles((unsigned)n_tiles, (unsigned)n_recs), one(1, (unsigned)n_recs);
+    hipLaunchKernelGGL((k_affine_scan<PP, DC, 0>), tiles, dim3(kAffBlock), 0, ctx->stream, dr, h, n_tiles);
+    hipLaunchKernelGGL((k_affine_scan<PP, DC, 1>), one, dim3(kAffBlock), 0, ctx->stream, dr, h, n_tiles);
+    hipLaunchKernelGGL((k_affine_scan<PP, DC, 2>), tiles, dim3(kAffBlock), 0, ctx->stream, dr, h, n_tiles);
+  }
+  P3R_HIP(hipGetLastError());
+  if (last_out) {
+    std::vector<uint32_t> raw(n_recs * kAffMaxDC);
+    P3R_HIP(fetch_small(ctx, d_last.p, raw.size(), raw.data()));   // waits for the stream
+    for (size_t i = 0; i < n_recs; ++i)
+      for (int k = 0; k < kAffMaxDC; ++k)
+        last_out[i * kAffMaxDC + k] = k < ((plan.form[i] & AFF_EXT) ? DC : 1) ? F::raw(raw[i * kAffMaxDC + k]).to_canonical() : 0u;
+  }
+  // the scratch and the descriptors go back to the context's pool, which is ordered by the stream the launches are on
   return out;
 }
 
@@ -797,6 +864,16 @@ std::unique_ptr<p3r_dmat> witness_program(p3r_ctx* ctx, const p3r_air_insn* prog
   return witness_program_dc<PP, 4>(ctx, prog, n_insns, mats, height, publics, n_public, challenges, n_challenges);
 }
 
+template <class PP>
+std::unique_ptr<p3r_dmat> affine_scan(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs, const std::vector<const p3r_dmat*>& mats,
+                                      uint32_t* last_out) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>) return affine_scan_dc<PP, 5>(ctx, recs, n_recs, mats, last_out);
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  return affine_scan_dc<PP, 4>(ctx, recs, n_recs, mats, last_out);
+}
+
 #define P3R_AIR_INSTANCE(PP)                                                                                                     \
   template std::vector<std::unique_ptr<p3r_dmat>> quotient_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t,                    \
                                                                        const std::vector<const p3r_dmat*>&, uint32_t, uint32_t, \
@@ -827,5 +904,11 @@ P3R_CHECK_INSTANCE(BabyBearParams)
 P3R_WITNESS_INSTANCE(KoalaBearParams)
 P3R_WITNESS_INSTANCE(BabyBearParams)
 #undef P3R_WITNESS_INSTANCE
+#define P3R_SCAN_INSTANCE(PP)                                                                                                       \
+  template std::unique_ptr<p3r_dmat> affine_scan<PP>(p3r_ctx*, const p3r_recurrence*, size_t, const std::vector<const p3r_dmat*>&,  \
+                                                     uint32_t*);
+P3R_SCAN_INSTANCE(KoalaBearParams)
+P3R_SCAN_INSTANCE(BabyBearParams)
+#undef P3R_SCAN_INSTANCE
 
 }  // namespace p3r

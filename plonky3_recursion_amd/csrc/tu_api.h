@@ -169,6 +169,14 @@ std::unique_ptr<p3r_dmat> witness_program(p3r_ctx* ctx, const p3r_air_insn* prog
                                           size_t height, const uint32_t* publics, size_t n_public, const uint32_t* challenges,
                                           size_t n_challenges);
 
+// Accumulator columns of a caller's trace (tu_air.hip): the recurrences `recs` (s[r + 1] = a[r] s[r] + b[r], a and b columns
+// of the traces `mats`: one height h, natural order) as the columns of a fresh h x W matrix.  `last_out` (host, n_recs x 5,
+// may be NULL): s[h] of each, canonical; with it the call waits for the stream, without it it only enqueues.  Everything
+// that is refused is refused before anything is allocated or launched (include/p3r.h lists it; scan_plan.h decides it).
+template <class PP>
+std::unique_ptr<p3r_dmat> affine_scan(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs, const std::vector<const p3r_dmat*>& mats,
+                                      uint32_t* last_out);
+
 // K7 / K8 launches (tu_logup.hip, tu_quotient.hip): the instance of the context's circuit degree
 template <class PP, int DC>
 void launch_logup_aux(p3r_ctx* ctx, unsigned blocks, const LogupJob* d_jobs, int n_jobs, const LookupChT<DC>& lc);

@@ -626,6 +626,46 @@ def witness_program_info(cfg, program, widths):
     return {k: int(getattr(info, k)) for k, _ in _lib.P3rWitnessInfo._fields_}
 
 
+class Recurrence:
+    """One p3r_recurrence of Context.affine_scan_device: s[0] = init, s[r + 1] = a[r] * s[r] + b[r].  `mul` and `add` are
+    (matrix, column) pairs - the first of DC consecutive columns with ext=True - or None: no `mul` is a = 1 everywhere (a
+    running sum), no `add` is b = 0 everywhere (a running product).  `out_col`: the (first) output column.  `init`: a
+    canonical word, or up to DC of them for an extension recurrence.  `inclusive`: row r holds s[r + 1] instead of s[r]."""
+
+    def __init__(self, out_col, mul=None, add=None, init=0, ext=False, inclusive=False):
+        self.out_col, self.mul, self.add, self.ext, self.inclusive = int(out_col), mul, add, bool(ext), bool(inclusive)
+        self.init = [int(v) for v in np.atleast_1d(init)]
+
+    def raw(self):
+        none = (_lib.P3R_SCAN_NONE, 0)
+        (mm, mc), (am, ac) = self.mul or none, self.add or none
+        if len(self.init) > 5:
+            raise ValueError("init has at most 5 words")
+        return _lib.P3rRecurrence((_lib.P3R_SCAN_EXT if self.ext else 0) | (_lib.P3R_SCAN_INCLUSIVE if self.inclusive else 0),
+                                  int(mm), int(mc), int(am), int(ac), self.out_col, (C.c_uint32 * 5)(*self.init))
+
+
+def _recurrences(recurrences):
+    """(array of p3r_recurrence, n) from Recurrence objects, dicts of Recurrence's arguments or raw P3rRecurrence structs."""
+    raws = [r if isinstance(r, _lib.P3rRecurrence) else (Recurrence(**r) if isinstance(r, dict) else r).raw() for r in recurrences]
+    return (_lib.P3rRecurrence * max(1, len(raws)))(*raws), len(raws)
+
+
+def affine_scan_info(cfg, recurrences, widths):
+    """p3r_affine_scan_info on the host (no GPU): validates the `recurrences` (as Context.affine_scan_device takes them)
+    against the matrix `widths` under the field and challenge degree of the p3r_config `cfg`; returns a dict of
+    n_out_columns (the width of the matrix affine_scan_device returns), n_products, n_sums and n_affine.  Raises P3rError
+    with the reason when they are refused."""
+    lib = _lib.load()
+    arr, n = _recurrences(recurrences)
+    ws = (C.c_size_t * max(1, len(widths)))(*[int(w) for w in widths])
+    info = _lib.P3rScanInfo()
+    rc = lib.p3r_affine_scan_info(C.byref(cfg), arr, n, ws, len(widths), C.byref(info))
+    if rc != 0:
+        raise P3rError(rc, lib.p3r_last_error(None).decode())
+    return {k: int(getattr(info, k)) for k, _ in _lib.P3rScanInfo._fields_}
+
+
 class Context:
     """One per GPU; not thread-safe; one call in flight (include/p3r.h)."""
 
@@ -1031,6 +1071,28 @@ class Context:
         self.check(self.lib.p3r_witness_program_dmat(self.h, arr, n, mats, len(dmats), 0 if height is None else int(height), pvp, pv.size,
                                                      chp, len(ch), C.byref(out)))
         return DeviceMatrix(self, self.ptr(out.value))
+
+    # ---- accumulator columns: first-order affine recurrences down the rows of resident traces
+    def affine_scan_info(self, recurrences, widths):
+        """affine_scan_info under this context's field and challenge degree."""
+        return affine_scan_info(self.cfg, recurrences, widths)
+
+    def affine_scan_device(self, recurrences, dmats, want_last=False):
+        """The accumulator columns s[0] = init, s[r + 1] = a[r] * s[r] + b[r] of the `recurrences` (Recurrence objects, or
+        dicts of Recurrence's arguments) over the traces `dmats`: one height h, natural row order, not LDEs.  Returns a new
+        (h, W) DeviceMatrix, W one past the highest written column; row r holds s[r], the state entering the row, or
+        s[r + 1] for an inclusive recurrence.  A trace like any other, for coset_lde_batch_device and check_device.  With
+        `want_last` returns (matrix, last): `last` an (n, 5) uint32 array of s[h] per recurrence, canonical, DC words used
+        for an extension recurrence and one otherwise, the rest zero - and the call waits for the stream.  Without it the
+        call only enqueues.  The inputs are left as they are."""
+        arr, n = _recurrences(recurrences)
+        mats = (C.c_void_p * max(1, len(dmats)))(*[d.h for d in dmats])
+        out = C.c_void_p()
+        last = np.zeros((n, 5), dtype=np.uint32) if want_last else None
+        self.check(self.lib.p3r_affine_scan_dmat(self.h, arr, n, mats, len(dmats), C.byref(out),
+                                                 last.ctypes.data_as(_lib.u32p) if want_last else None))
+        dm = DeviceMatrix(self, self.ptr(out.value))
+        return (dm, last) if want_last else dm
 
     # ---- the rest of prove_fri: challenger, commit-phase leaf view, final polynomial, schedule, and their composition
     def challenger(self):
