@@ -4,19 +4,21 @@
 //   k_quotient_program   p3r_quotient_program_dmat: the caller's constraints on every row of the quotient domain of resident
 //                        LDEs.  The prover's own k_quotient (kernels_stark.hip.h) keeps its constraint systems inlined; this
 //                        kernel is the same pass with the constraints as data.
-//   k_logup_program      p3r_logup_program_dmat: the caller's lookups on every row of resident TRACES - the fraction columns
-//                        of the permutation trace and each row's total; the running sum is k_ef_scan's (kernels_stark.hip.h).
-//                        The prover's own k_logup_aux keeps the interactions of the built-in tables inlined.
-//   k_check_program      p3r_check_program_dmat: the caller's constraints on every row of resident TRACES with 0 / 1
-//                        selectors - per constraint the smallest row in which it does not vanish and the number of such rows.
-//   k_lookup_records     p3r_lookup_check_dmat: the caller's lookups on every row of resident TRACES - every term's
-//                        denominator and multiplicity as canonical words, for the sort and the sums of tu_air.hip.
-//   k_witness_program    p3r_witness_program_dmat: the caller's derived columns on every row of resident TRACES - values
-//                        stored as the columns of a new trace, with the value ops witness generation needs and
-//                        constraints must not have (inverse-or-zero, bit fields of the canonical word, the row index).
+//   k_trace_program      the caller's program on every row of resident TRACES, natural order; what becomes of the values
+//                        is its sink's:
+//     LogupProgSink      p3r_logup_program_dmat: the fraction columns of the permutation trace and each row's total; the
+//                        running sum is k_ef_scan's (kernels_stark.hip.h).  The prover's own k_logup_aux keeps the
+//                        interactions of the built-in tables inlined.
+//     CheckProgSink      p3r_check_program_dmat: constraints with 0 / 1 selectors - per constraint the smallest row in
+//                        which it does not vanish and the number of such rows.
+//     RecordSink         p3r_lookup_check_dmat, p3r_lookup_multiplicities_dmat: every term's denominator and multiplicity
+//                        as canonical words, for the sort and the sums of tu_air.hip.
+//     WitnessSink        p3r_witness_program_dmat: values stored as the columns of a new trace, with the value ops witness
+//                        generation needs and constraints must not have (inverse-or-zero, bit fields of the canonical
+//                        word, the row index).
 //
-// All five are one interpreter, air_step, with the sinks as a template parameter (QuotProgSink / LogupProgSink /
-// CheckProgSink / RecordSink / WitnessSink), as AuxSink / QuotSink share air_interactions for the built-in AIRs.
+// Both are one interpreter - air_run, the loop over air_step - with the sinks as a template parameter, as AuxSink /
+// QuotSink share air_interactions for the built-in AIRs.
 //
 // One lane per row: of the quotient domain in storage (bit-reversed) order, of a trace in natural order - either way the
 // read of a column at the current row is one contiguous run per wave; the next row's read is the same run bit-reversal
@@ -46,27 +48,21 @@ struct AirChunkTables {
   uint32_t zh[1 << kAirMaxLogChunks], zh_inv[1 << kAirMaxLogChunks];   // AirDomain's
   uint32_t* out[1 << kAirMaxLogChunks];                                // chunk c: [DC][h], natural order
 };
-struct AirProgArgs {
+// What every interpreter reads: the first member of every argument struct.
+struct AirStream {
   const AirDevInsn* insns;         // n_insns of them
   const uint32_t* ext_consts;      // Montgomery, DC words per entry
-  const uint32_t* const* cols;     // one pointer per flat column: H words, bit-reversed rows
-  const AirChunkTables* chunks;
+  const uint32_t* const* cols;     // one pointer per flat column: the rows of a trace in natural order, of an LDE bit-reversed
   uint32_t n_insns;
+};
+struct AirProgArgs {
+  AirStream prog;
+  const AirChunkTables* chunks;
   int log_n;                       // log2 of the quotient domain N = h * 2^log_q
   int log_q;
   uint32_t flags;                  // 1: a selector is read (x is needed); 2: is_first_row / is_last_row (the inversions)
   uint32_t shift, w_n, g_inv;      // AirDomain's
   uint32_t alpha[kMaxAirDC];
-};
-struct AirLogupArgs {
-  const AirDevInsn* insns;         // n_insns of them
-  const uint32_t* ext_consts;      // Montgomery, DC words per entry
-  const uint32_t* const* cols;     // one pointer per flat column: h words, natural order
-  uint32_t* out;                   // [DC * (1 + G)][h]: the fraction columns are written here, the first DC by k_ef_scan
-  uint32_t* rowsum;                // [DC][h]: sum_g f_g of the row
-  uint32_t* bad_row;               // one word, 0xffffffff before the launch: the smallest row with a zero denominator
-  uint32_t n_insns;
-  int log_h;
 };
 
 // A lane's slot file: word w is s[w * kAirLanes].
@@ -137,18 +133,43 @@ __device__ __forceinline__ void air_step(const AirDevInsn& in, const AirSlots<PP
   }
 }
 
+// A whole stream over one lane's slots (lane_slots: word 0 of the lane), current / next rows j / j_next, into `sink`.
+template <class PP, int DC, class Sink>
+__device__ __forceinline__ void air_run(const AirStream& prog, uint32_t* lane_slots, size_t j, size_t j_next, Sink& sink) {
+  const AirSlots<PP, DC> sl{lane_slots};
+  const gptr<const AirDevInsn> insns = as_global(prog.insns);
+  const gptr<const uint32_t> ext_consts = as_global(prog.ext_consts);
+  const gptr<const uint32_t* const> cols = as_global(prog.cols);
+  for (uint32_t pc = 0; pc < prog.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, j, j_next, sink);
+}
+
+// The selectors of a lane's row.  On the quotient domain they are k_quotient_program's values at the lane's point; on the
+// trace domain 0 / 1 by the row (DebugConstraintBuilder's).  The three ops that store them stay case labels of each sink's
+// one switch: served from here - by a nested switch, or by a test before the sink's switch - the interpreters of these
+// sinks ran 10 to 15 % slower (profiles/r22/program_seams.txt), and a select between the members put them into scratch.
+template <class PP, int DC>
+struct AirSelectors {
+  using F = Fp<PP>;
+  F is_first, is_last, is_transition;
+  __device__ __forceinline__ void of_trace_row(size_t r, size_t h) {
+    is_first = r == 0 ? F::one() : F::zero();
+    is_last = r == h - 1 ? F::one() : F::zero();
+    is_transition = r == h - 1 ? F::zero() : F::one();
+  }
+};
+
 // The sinks of a constraint program: the selectors of the lane's point, and the Horner fold of the asserted values.
 template <class PP, int DC>
 struct QuotProgSink {
   using F = Fp<PP>;
   using E = typename Chal<PP, DC>::type;
-  F is_first, is_last, is_transition;
+  AirSelectors<PP, DC> sel;
   E alpha, acc;
   __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
     switch (in.op) {
-      case AIR_D_FIRST: sl.st(in.dst, is_first); break;
-      case AIR_D_LAST: sl.st(in.dst, is_last); break;
-      case AIR_D_TRANS: sl.st(in.dst, is_transition); break;
+      case AIR_D_FIRST: sl.st(in.dst, sel.is_first); break;
+      case AIR_D_LAST: sl.st(in.dst, sel.is_last); break;
+      case AIR_D_TRANS: sl.st(in.dst, sel.is_transition); break;
       case AIR_D_ASSERT_B: acc = acc * alpha; acc.c[0] += sl.ld(in.a); break;
       case AIR_D_ASSERT_E: acc = acc * alpha + sl.lde(in.a); break;
       default: break;   // air_compile emits nothing else for a constraint program
@@ -170,27 +191,24 @@ __global__ void __launch_bounds__(kAirLanes) k_quotient_program(AirProgArgs a) {
   const size_t j_next = bit_reverse((uint32_t)((i + n_chunks) & (n_rows - 1)), a.log_n);
   const gptr<const AirChunkTables> chunks = as_global(a.chunks);
   QuotProgSink<PP, DC> sink;
-  sink.is_first = sink.is_last = sink.is_transition = F::zero();
+  AirSelectors<PP, DC>& sel = sink.sel;
+  sel.is_first = sel.is_last = sel.is_transition = F::zero();
   if (a.flags & 1u) {
     const F x = F::raw(a.shift) * F::raw(a.w_n).pow(i);
-    sink.is_transition = x - F::raw(a.g_inv);
+    sel.is_transition = x - F::raw(a.g_inv);
     if (a.flags & 2u) {
       // x - 1 and x - w_h^-1 are roots of x^h - 1, which has no zero in the domain (air_domain): one shared inversion
       const F xm1 = x - F::one();
-      const F t = (xm1 * sink.is_transition).inv() * F::raw(chunks->zh[c]);
-      sink.is_first = t * sink.is_transition;
-      sink.is_last = t * xm1;
+      const F t = (xm1 * sel.is_transition).inv() * F::raw(chunks->zh[c]);
+      sel.is_first = t * sel.is_transition;
+      sel.is_last = t * xm1;
     }
   }
   sink.acc = E::zero();
 #pragma unroll
   for (int k = 0; k < DC; ++k) sink.alpha.c[k] = F::raw(a.alpha[k]);
 
-  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
-  const gptr<const AirDevInsn> insns = as_global(a.insns);
-  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
-  const gptr<const uint32_t* const> cols = as_global(a.cols);
-  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, j, j_next, sink);
+  air_run<PP, DC>(a.prog, air_slots + threadIdx.x, j, j_next, sink);
   const E quot = sink.acc * F::raw(chunks->zh_inv[c]);
   const size_t h = n_rows >> a.log_q, r = i >> a.log_q;
   uint32_t* out = chunks->out[c];
@@ -198,19 +216,56 @@ __global__ void __launch_bounds__(kAirLanes) k_quotient_program(AirProgArgs a) {
   for (int k = 0; k < DC; ++k) as_global(out)[(size_t)k * h + r] = quot.c[k].v;
 }
 
+// A program on the rows of TRACES in natural order, the next row wrapping at the height.  The sink brings its argument
+// struct (Args: an AirStream `prog`, `log_h`, and what it writes to), how it starts on a row (init) and what it writes after
+// the last instruction (done: the LogUp sink's row total, nothing elsewhere).  A lane past the end returns before its sink
+// exists: with h < 64 the check sink's ballots see the active lanes only.
+template <class PP, int DC, template <class, int> class Sink>
+__global__ void __launch_bounds__(kAirLanes) k_trace_program(typename Sink<PP, DC>::Args a) {
+  extern __shared__ uint32_t air_slots[];
+  const size_t h = size_t(1) << a.log_h;
+  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;
+  if (r >= h) return;
+  Sink<PP, DC> sink;
+  sink.init(a, r, h);
+  air_run<PP, DC>(a.prog, air_slots + threadIdx.x, r, (r + 1) & (h - 1), sink);
+  sink.done(a);
+}
+
 // The sinks of a lookup program.  The open column's fraction is kept as num / den in registers: a term m / d does
 // num <- num * d + m * den, den <- den * d, and the end of the column the one inversion f = num * den^-1 - one per
 // column, not per term.  f goes to words [col * DC + k][row] of the output (consecutive lanes, consecutive words) and
 // into the row's total.  A lane whose den is zero - upstream divides by zero there - records its row in *bad_row
 // (the smallest wins) and writes zeros; the host refuses the call then (tu_air.hip).
+struct AirLogupArgs {
+  AirStream prog;
+  int log_h;
+  uint32_t* out;                   // [DC * (1 + G)][h]: the fraction columns are written here, the first DC by k_ef_scan
+  uint32_t* rowsum;                // [DC][h]: sum_g f_g of the row
+  uint32_t* bad_row;               // one word, 0xffffffff before the launch: the smallest row with a zero denominator
+};
 template <class PP, int DC>
 struct LogupProgSink {
+  using Args = AirLogupArgs;
   using F = Fp<PP>;
   using E = typename Chal<PP, DC>::type;
   gptr<uint32_t> out;
   uint32_t* bad_row;
   size_t h, row;
   E num, den, total;
+  __device__ __forceinline__ void init(const Args& a, size_t r, size_t h_) {
+    out = as_global(a.out);
+    bad_row = a.bad_row;
+    h = h_;
+    row = r;
+    num = total = E::zero();
+    den = E::one();
+  }
+  __device__ __forceinline__ void done(const Args& a) const {
+    const gptr<uint32_t> rowsum = as_global(a.rowsum);
+#pragma unroll
+    for (int k = 0; k < DC; ++k) rowsum[(size_t)k * h + row] = total.c[k].v;
+  }
   __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
     switch (in.op) {
       case AIR_D_TERM_BB: { const F m = sl.ld(in.a), d = sl.ld(in.b); num = num * d + den * m; den = den * d; break; }
@@ -233,47 +288,34 @@ struct LogupProgSink {
   }
 };
 
-template <class PP, int DC>
-__global__ void __launch_bounds__(kAirLanes) k_logup_program(AirLogupArgs a) {
-  using E = typename Chal<PP, DC>::type;
-  extern __shared__ uint32_t air_slots[];
-  const size_t h = size_t(1) << a.log_h;
-  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
-  if (r >= h) return;
-  const size_t r_next = (r + 1) & (h - 1);
-  LogupProgSink<PP, DC> sink;
-  sink.out = as_global(a.out);
-  sink.bad_row = a.bad_row;
-  sink.h = h;
-  sink.row = r;
-  sink.num = sink.total = E::zero();
-  sink.den = E::one();
-
-  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
-  const gptr<const AirDevInsn> insns = as_global(a.insns);
-  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
-  const gptr<const uint32_t* const> cols = as_global(a.cols);
-  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
-  const gptr<uint32_t> rowsum = as_global(a.rowsum);
-#pragma unroll
-  for (int k = 0; k < DC; ++k) rowsum[(size_t)k * h + r] = sink.total.c[k].v;
-}
-
 // The sinks of a constraint program on the trace domain (DebugConstraintBuilder): the selectors are 0 / 1 by the lane's
 // row, and an asserted value is looked at, not folded.  Every lane of the wave stands at the same ASSERT (the instruction
 // stream is wave-uniform), so one ballot of "not zero" over the wave's active lanes says whether any row failed; only then
 // does ONE lane - the lowest failing one - add the popcount to the constraint's counter and offer the wave's smallest
 // failing row to its first_row.  At most two atomics per wave and constraint, none at all on a satisfying trace.
 // The constraint's ordinal is counted here: one ASSERT, one increment, the same in every lane.
+struct AirCheckArgs {
+  AirStream prog;
+  int log_h;
+  uint32_t* first_row;             // [n_constraints], 0xffffffff before the launch
+  unsigned long long* n_failed;    // [n_constraints], 0 before the launch
+};
 template <class PP, int DC>
 struct CheckProgSink {
-  using F = Fp<PP>;
-  using E = typename Chal<PP, DC>::type;
-  F is_first, is_last, is_transition;
+  using Args = AirCheckArgs;
+  AirSelectors<PP, DC> sel;
   uint32_t* first_row;
   unsigned long long* n_failed;
   uint32_t wave_row;   // the row of the wave's lane 0
   uint32_t k;          // constraints met so far
+  __device__ __forceinline__ void init(const Args& a, size_t r, size_t h) {
+    sel.of_trace_row(r, h);
+    first_row = a.first_row;
+    n_failed = a.n_failed;
+    wave_row = blockIdx.x * (uint32_t)kAirLanes;
+    k = 0;
+  }
+  __device__ __forceinline__ void done(const Args&) const {}
   __device__ __forceinline__ void vote(bool bad) {
     const uint64_t failing = __ballot(bad);
     if (failing) {
@@ -287,9 +329,9 @@ struct CheckProgSink {
   }
   __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
     switch (in.op) {
-      case AIR_D_FIRST: sl.st(in.dst, is_first); break;
-      case AIR_D_LAST: sl.st(in.dst, is_last); break;
-      case AIR_D_TRANS: sl.st(in.dst, is_transition); break;
+      case AIR_D_FIRST: sl.st(in.dst, sel.is_first); break;
+      case AIR_D_LAST: sl.st(in.dst, sel.is_last); break;
+      case AIR_D_TRANS: sl.st(in.dst, sel.is_transition); break;
       case AIR_D_ASSERT_B: vote(sl.ld(in.a).v != 0); break;
       case AIR_D_ASSERT_E: vote(!sl.lde(in.a).is_zero()); break;
       default: break;   // air_compile emits nothing else for a constraint program
@@ -297,51 +339,35 @@ struct CheckProgSink {
   }
 };
 
-struct AirCheckArgs {
-  const AirDevInsn* insns;         // n_insns of them
-  const uint32_t* ext_consts;      // Montgomery, DC words per entry
-  const uint32_t* const* cols;     // one pointer per flat column: h words, natural order
-  uint32_t* first_row;             // [n_constraints], 0xffffffff before the launch
-  unsigned long long* n_failed;    // [n_constraints], 0 before the launch
-  uint32_t n_insns;
-  int log_h;
-};
-
-template <class PP, int DC>
-__global__ void __launch_bounds__(kAirLanes) k_check_program(AirCheckArgs a) {
-  using F = Fp<PP>;
-  extern __shared__ uint32_t air_slots[];
-  const size_t h = size_t(1) << a.log_h;
-  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
-  if (r >= h) return;   // h < 64: the ballots see the active lanes only
-  const size_t r_next = (r + 1) & (h - 1);
-  CheckProgSink<PP, DC> sink;
-  sink.is_first = r == 0 ? F::one() : F::zero();
-  sink.is_last = r == h - 1 ? F::one() : F::zero();
-  sink.is_transition = r == h - 1 ? F::zero() : F::one();
-  sink.first_row = a.first_row;
-  sink.n_failed = a.n_failed;
-  sink.wave_row = blockIdx.x * (uint32_t)kAirLanes;
-  sink.k = 0;
-
-  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
-  const gptr<const AirDevInsn> insns = as_global(a.insns);
-  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
-  const gptr<const uint32_t* const> cols = as_global(a.cols);
-  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
-}
-
 // The sinks of a lookup program whose terms are recorded, not summed: term t of row r is slot base + r * n_terms + t of
 // the call - the slots of a call are its records in record order (instance, row, term) - and writes the canonical words
 // of its denominator and multiplicity, both lifted, to [word][slot], and whether the multiplicity is not zero to
 // mark[slot].  Nothing is inverted and a column end does nothing.  The lanes of a wave write n_terms words apart; the
 // n_terms writes of a row fill the lines between.  The term's ordinal is counted here, as CheckProgSink counts constraints.
+struct AirRecordArgs {
+  AirStream prog;
+  int log_h;
+  uint32_t n_terms;                // LOOKUPs of the program
+  uint32_t* den;                   // [DC][n_slots], canonical
+  uint32_t* mul;                   // [DC][n_slots], canonical
+  uint32_t* mark;                  // [n_slots]
+  size_t n_slots;                  // of the whole call
+  size_t base;                     // first slot of this instance
+};
 template <class PP, int DC>
 struct RecordSink {
-  using F = Fp<PP>;
+  using Args = AirRecordArgs;
   using E = typename Chal<PP, DC>::type;
   gptr<uint32_t> den, mul, mark;
   size_t n_slots, slot;   // slot: of the row's next term
+  __device__ __forceinline__ void init(const Args& a, size_t r, size_t) {
+    den = as_global(a.den);
+    mul = as_global(a.mul);
+    mark = as_global(a.mark);
+    n_slots = a.n_slots;
+    slot = a.base + r * a.n_terms;
+  }
+  __device__ __forceinline__ void done(const Args&) const {}
   __device__ __forceinline__ void put(const E& m, const E& d) {
 #pragma unroll
     for (int k = 0; k < DC; ++k) {
@@ -362,59 +388,37 @@ struct RecordSink {
   }
 };
 
-struct AirRecordArgs {
-  const AirDevInsn* insns;         // n_insns of them
-  const uint32_t* ext_consts;      // Montgomery, DC words per entry
-  const uint32_t* const* cols;     // one pointer per flat column: h words, natural order
-  uint32_t* den;                   // [DC][n_slots], canonical
-  uint32_t* mul;                   // [DC][n_slots], canonical
-  uint32_t* mark;                  // [n_slots]
-  size_t n_slots;                  // of the whole call
-  size_t base;                     // first slot of this instance
-  uint32_t n_terms;                // LOOKUPs of the program
-  uint32_t n_insns;
-  int log_h;
-};
-
-template <class PP, int DC>
-__global__ void __launch_bounds__(kAirLanes) k_lookup_records(AirRecordArgs a) {
-  extern __shared__ uint32_t air_slots[];
-  const size_t h = size_t(1) << a.log_h;
-  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
-  if (r >= h) return;
-  const size_t r_next = (r + 1) & (h - 1);
-  RecordSink<PP, DC> sink;
-  sink.den = as_global(a.den);
-  sink.mul = as_global(a.mul);
-  sink.mark = as_global(a.mark);
-  sink.n_slots = a.n_slots;
-  sink.slot = a.base + r * a.n_terms;
-
-  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
-  const gptr<const AirDevInsn> insns = as_global(a.insns);
-  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
-  const gptr<const uint32_t* const> cols = as_global(a.cols);
-  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
-}
-
 // The sinks of a witness program: values become columns.  The selectors are CheckProgSink's 0 / 1.  INV is the field's own
 // inverse - Fp::inv is x^(p-2) and the extension inverses multiply by the inverse of a norm, so 0 comes out as 0 with no
 // guard: the try_inverse().unwrap_or_default() of an is-zero witness.  BITS leaves Montgomery form (one multiplication
 // by 1), shifts and masks the canonical word, and re-enters (one multiplication by R^2); ROW enters the same way (a row is
 // below 2^TWO_ADICITY < p).  A STORE writes word out[col * h + row]: the 64 lanes of the wave write 64 consecutive words of
 // one column, plain vector stores; air_plan has seen to it that every column below the output's width has one writer.
+struct AirWitnessArgs {
+  AirStream prog;
+  int log_h;
+  uint32_t* out;                   // [W][h]: the stored columns
+};
 template <class PP, int DC>
 struct WitnessSink {
+  using Args = AirWitnessArgs;
   using F = Fp<PP>;
   using E = typename Chal<PP, DC>::type;
-  F is_first, is_last, is_transition;
+  AirSelectors<PP, DC> sel;
   gptr<uint32_t> out;
   size_t h, row;
+  __device__ __forceinline__ void init(const Args& a, size_t r, size_t h_) {
+    sel.of_trace_row(r, h_);
+    out = as_global(a.out);
+    h = h_;
+    row = r;
+  }
+  __device__ __forceinline__ void done(const Args&) const {}
   __device__ __forceinline__ void step(const AirDevInsn& in, const AirSlots<PP, DC>& sl) {
     switch (in.op) {
-      case AIR_D_FIRST: sl.st(in.dst, is_first); break;
-      case AIR_D_LAST: sl.st(in.dst, is_last); break;
-      case AIR_D_TRANS: sl.st(in.dst, is_transition); break;
+      case AIR_D_FIRST: sl.st(in.dst, sel.is_first); break;
+      case AIR_D_LAST: sl.st(in.dst, sel.is_last); break;
+      case AIR_D_TRANS: sl.st(in.dst, sel.is_transition); break;
       case AIR_D_INV_B: sl.st(in.dst, sl.ld(in.a).inv()); break;
       case AIR_D_INV_E: sl.ste(in.dst, sl.lde(in.a).inv()); break;
       case AIR_D_BITS: {
@@ -434,37 +438,5 @@ struct WitnessSink {
     }
   }
 };
-
-struct AirWitnessArgs {
-  const AirDevInsn* insns;         // n_insns of them
-  const uint32_t* ext_consts;      // Montgomery, DC words per entry
-  const uint32_t* const* cols;     // one pointer per flat input column: h words, natural order
-  uint32_t* out;                   // [W][h]: the stored columns
-  uint32_t n_insns;
-  int log_h;
-};
-
-template <class PP, int DC>
-__global__ void __launch_bounds__(kAirLanes) k_witness_program(AirWitnessArgs a) {
-  using F = Fp<PP>;
-  extern __shared__ uint32_t air_slots[];
-  const size_t h = size_t(1) << a.log_h;
-  const size_t r = (size_t)blockIdx.x * kAirLanes + threadIdx.x;   // trace row, natural order
-  if (r >= h) return;
-  const size_t r_next = (r + 1) & (h - 1);
-  WitnessSink<PP, DC> sink;
-  sink.is_first = r == 0 ? F::one() : F::zero();
-  sink.is_last = r == h - 1 ? F::one() : F::zero();
-  sink.is_transition = r == h - 1 ? F::zero() : F::one();
-  sink.out = as_global(a.out);
-  sink.h = h;
-  sink.row = r;
-
-  const AirSlots<PP, DC> sl{air_slots + threadIdx.x};
-  const gptr<const AirDevInsn> insns = as_global(a.insns);
-  const gptr<const uint32_t> ext_consts = as_global(a.ext_consts);
-  const gptr<const uint32_t* const> cols = as_global(a.cols);
-  for (uint32_t pc = 0; pc < a.n_insns; ++pc) air_step<PP, DC>(air_fetch(insns, pc), sl, ext_consts, cols, r, r_next, sink);
-}
 
 }  // namespace p3r

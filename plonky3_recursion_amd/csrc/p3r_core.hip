@@ -582,6 +582,15 @@ int p3r_coset_lde(p3r_ctx* ctx, const uint32_t* evals, size_t h, size_t w, uint3
   });
 }
 
+// A caller's array of matrix handles, none of them NULL.  `who` leads the refusal where the array is one of several
+// ("instance 2: ", "table: ").
+static std::vector<const p3r_dmat*> checked_mats(const p3r_dmat* const* mats, size_t n_mats, const char* who = "") {
+  if (n_mats && !mats) fail(P3R_EINVAL, "%smats is NULL", who);
+  for (size_t i = 0; i < n_mats; ++i)
+    if (!mats[i]) fail(P3R_EINVAL, "%smatrix %zu is NULL", who, i);
+  return std::vector<const p3r_dmat*>(mats, mats + n_mats);
+}
+
 // TwoAdicSubgroupDft::dft_batch / idft_batch / coset_dft_batch / coset_idft_batch: one half of the LDE (tu_lde.hip)
 static void dft_check_modes(uint32_t direction, uint32_t eval_order) {
   if (direction != P3R_DFT_FORWARD && direction != P3R_DFT_INVERSE) fail(P3R_EINVAL, "unknown DFT direction %u", direction);
@@ -592,11 +601,9 @@ int p3r_dft_batch_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats,
   return guard(ctx, [&] {
     if (!mats || !shifts || !outs || n_mats == 0) fail(P3R_EINVAL, "bad arguments");
     dft_check_modes(direction, eval_order);
+    const auto ms = checked_mats(mats, n_mats);
     std::vector<LdeItem> items(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      items[i] = {mats[i], shifts[i]};
-    }
+    for (size_t i = 0; i < n_mats; ++i) items[i] = {ms[i], shifts[i]};
     auto res = P3R_FIELD_CALL(ctx, dft_batch, ctx, items, direction == P3R_DFT_INVERSE, eval_order == P3R_DFT_BITREV);
     for (size_t i = 0; i < n_mats; ++i) outs[i] = res[i].release();
   });
@@ -628,11 +635,9 @@ int p3r_open_points_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mat
     if (n_mats == 0) return;
     if (!mats) fail(P3R_EINVAL, "mats is NULL");
     open_points_check_modes(added_bits, eval_order, point_offsets);
+    const auto ms = checked_mats(mats, n_mats);
     std::vector<OpenPointsItem> items(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      items[i] = {mats[i]->d, mats[i]->h, mats[i]->w, point_offsets[i], point_offsets[i + 1]};
-    }
+    for (size_t i = 0; i < n_mats; ++i) items[i] = {ms[i]->d, ms[i]->h, ms[i]->w, point_offsets[i], point_offsets[i + 1]};
     P3R_FIELD_CALL(ctx, open_points, ctx, items, (int)added_bits, shift, eval_order == P3R_DFT_BITREV, points, values_out);
   });
 }
@@ -677,11 +682,9 @@ int p3r_fri_reduce_dmat(p3r_ctx* ctx, const p3r_dmat* const* mats, size_t n_mats
     if (n_outs) *n_outs = 0;
     if (n_mats == 0) fail(P3R_EINVAL, "n_mats == 0: no matrix to reduce");
     if (!mats || !point_offsets || !alpha || !outs || !n_outs) fail(P3R_EINVAL, "NULL argument");
+    const auto ms = checked_mats(mats, n_mats);
     std::vector<FriReduceItem> items(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      items[i] = {mats[i]->d, mats[i]->h, mats[i]->w, point_offsets[i], point_offsets[i + 1]};
-    }
+    for (size_t i = 0; i < n_mats; ++i) items[i] = {ms[i]->d, ms[i]->h, ms[i]->w, point_offsets[i], point_offsets[i + 1]};
     auto res = P3R_FIELD_CALL(ctx, fri_reduce, ctx, items, shift, points, values, alpha);
     for (size_t i = 0; i < res.size(); ++i) outs[i] = res[i].release();
     *n_outs = res.size();
@@ -807,16 +810,24 @@ int p3r_fri_log_arity(const p3r_ctx* ctx, size_t phase, int log_cur, int log_fin
   return fri_log_arity(ctx->fri_log_arities, phase, (int)ctx->cfg.max_log_arity, log_cur, log_final, log_next_input);
 }
 
+// The field and the challenge degree of a host-only entry's configuration: what is refused of them, the modulus and DC.
+struct HostField {
+  uint32_t p;
+  int dc;
+};
+static HostField host_field(const p3r_config* cfg) {
+  if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
+  if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
+    fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
+  return {cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P, cfg->challenge_degree == 5 ? 5 : 4};
+}
 // The caller's AIR as a constraint program: air_program.h (the host half), tu_air.hip (the launch)
 int p3r_air_program_info(const p3r_config* cfg, const p3r_air_insn* prog, size_t n_insns, const size_t* widths, size_t n_mats,
                          p3r_air_info* out) {
   return guard(nullptr, [&] {
     if (!cfg || !out) fail(P3R_EINVAL, "NULL argument");
-    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
-    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
-      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
-    const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
-    *out = air_plan(prog, n_insns, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p, kAirUnknownCount, kAirUnknownCount,
+    const HostField f = host_field(cfg);
+    *out = air_plan(prog, n_insns, widths, n_mats, f.dc, f.p, kAirUnknownCount, kAirUnknownCount,
                     P3R_AIR_MAX_LIVE).info;
   });
 }
@@ -827,15 +838,13 @@ int p3r_air_program_eval(const p3r_config* cfg, const p3r_air_insn* prog, size_t
                          uint32_t* inv_zh_out) {
   return guard(nullptr, [&] {
     if (!cfg) fail(P3R_EINVAL, "cfg is NULL");
-    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
-    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
-      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
+    const HostField f = host_field(cfg);
     if (cfg->zk) fail(P3R_EUNSUPPORTED, "zk configurations: their doubled domains are out of scope of the program seams");
     if (cfg->field == P3R_FIELD_BABY_BEAR) {
-      if (cfg->challenge_degree == 5) fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+      if (f.dc == 5) fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
       air_program_eval<BabyBearParams, 4>(prog, n_insns, widths, n_mats, local, next, log_height, zeta, public_values, n_public, challenges,
                                           n_challenges, alpha, folded_out, inv_zh_out);
-    } else if (cfg->challenge_degree == 5) {
+    } else if (f.dc == 5) {
       air_program_eval<KoalaBearParams, 5>(prog, n_insns, widths, n_mats, local, next, log_height, zeta, public_values, n_public, challenges,
                                            n_challenges, alpha, folded_out, inv_zh_out);
     } else {
@@ -850,12 +859,7 @@ int p3r_quotient_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_i
   return guard(ctx, [&] {
     if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
     if (!outs) fail(P3R_EINVAL, "outs is NULL");
-    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
-    std::vector<const p3r_dmat*> ms(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      ms[i] = mats[i];
-    }
+    const auto ms = checked_mats(mats, n_mats);
     auto res = P3R_FIELD_CALL(ctx, quotient_program, ctx, prog, n_insns, ms, added_bits, shift, log_quotient_degree, public_values,
                               n_public, challenges, n_challenges, alpha);
     for (size_t i = 0; i < res.size(); ++i) outs[i] = res[i].release();
@@ -867,11 +871,8 @@ int p3r_lookup_program_info(const p3r_config* cfg, const p3r_air_insn* prog, siz
                             p3r_lookup_info* out) {
   return guard(nullptr, [&] {
     if (!cfg || !out) fail(P3R_EINVAL, "NULL argument");
-    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
-    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
-      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
-    const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
-    *out = air_plan(prog, n_insns, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p, kAirUnknownCount, kAirUnknownCount,
+    const HostField f = host_field(cfg);
+    *out = air_plan(prog, n_insns, widths, n_mats, f.dc, f.p, kAirUnknownCount, kAirUnknownCount,
                     P3R_AIR_MAX_LIVE, AIR_MODE_LOOKUP).lookup;
   });
 }
@@ -882,12 +883,7 @@ int p3r_logup_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insn
     if (out) *out = nullptr;
     if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
     if (!out) fail(P3R_EINVAL, "out is NULL");
-    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
-    std::vector<const p3r_dmat*> ms(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      ms[i] = mats[i];
-    }
+    const auto ms = checked_mats(mats, n_mats);
     *out = P3R_FIELD_CALL(ctx, logup_program, ctx, prog, n_insns, ms, public_values, n_public, challenges, n_challenges, sum_out).release();
   });
 }
@@ -898,12 +894,7 @@ int p3r_check_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insn
                            p3r_check_report* report, uint32_t* first_row_out, uint64_t* n_failed_out) {
   return guard(ctx, [&] {
     if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
-    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
-    std::vector<const p3r_dmat*> ms(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      ms[i] = mats[i];
-    }
+    const auto ms = checked_mats(mats, n_mats);
     P3R_FIELD_CALL(ctx, check_program, ctx, prog, n_insns, ms, public_values, n_public, challenges, n_challenges, report, first_row_out,
                    n_failed_out);
   });
@@ -915,12 +906,9 @@ int p3r_lookup_check_dmat(p3r_ctx* ctx, const p3r_lookup_instance* inst, size_t 
     if (n_inst && !inst) fail(P3R_EINVAL, "inst is NULL");
     std::vector<LookupCheckInstance> is(n_inst);
     for (size_t p = 0; p < n_inst; ++p) {
-      if (inst[p].n_mats && !inst[p].mats) fail(P3R_EINVAL, "instance %zu: mats is NULL", p);
-      is[p] = LookupCheckInstance{inst[p].prog, inst[p].n_insns, {}, inst[p].public_values, inst[p].n_public};
-      for (size_t i = 0; i < inst[p].n_mats; ++i) {
-        if (!inst[p].mats[i]) fail(P3R_EINVAL, "instance %zu: matrix %zu is NULL", p, i);
-        is[p].mats.push_back(inst[p].mats[i]);
-      }
+      const std::string who = "instance " + std::to_string(p) + ": ";
+      is[p] = LookupCheckInstance{inst[p].prog, inst[p].n_insns, checked_mats(inst[p].mats, inst[p].n_mats, who.c_str()), inst[p].public_values,
+                                  inst[p].n_public};
     }
     P3R_FIELD_CALL(ctx, lookup_check, ctx, is, challenges, n_challenges, out, cap, n_unbalanced_out);
   });
@@ -937,13 +925,8 @@ int p3r_lookup_multiplicities_dmat(p3r_ctx* ctx, const p3r_lookup_instance* tabl
     std::vector<LookupCheckInstance> is(1 + n_queries);   // the table first
     for (size_t p = 0; p <= n_queries; ++p) {
       const p3r_lookup_instance& in = p ? queries[p - 1] : *table;
-      const std::string who = p ? "query " + std::to_string(p - 1) : std::string("table");
-      if (in.n_mats && !in.mats) fail(P3R_EINVAL, "%s: mats is NULL", who.c_str());
-      is[p] = LookupCheckInstance{in.prog, in.n_insns, {}, in.public_values, in.n_public};
-      for (size_t i = 0; i < in.n_mats; ++i) {
-        if (!in.mats[i]) fail(P3R_EINVAL, "%s: matrix %zu is NULL", who.c_str(), i);
-        is[p].mats.push_back(in.mats[i]);
-      }
+      const std::string who = p ? "query " + std::to_string(p - 1) + ": " : std::string("table: ");
+      is[p] = LookupCheckInstance{in.prog, in.n_insns, checked_mats(in.mats, in.n_mats, who.c_str()), in.public_values, in.n_public};
     }
     *out = P3R_FIELD_CALL(ctx, lookup_multiplicities, ctx, is, challenges, n_challenges, missing, cap, n_missing_out).release();
   });
@@ -954,11 +937,8 @@ int p3r_witness_program_info(const p3r_config* cfg, const p3r_air_insn* prog, si
                              p3r_witness_info* out) {
   return guard(nullptr, [&] {
     if (!cfg || !out) fail(P3R_EINVAL, "NULL argument");
-    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
-    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
-      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
-    const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
-    *out = air_plan(prog, n_insns, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p, kAirUnknownCount, kAirUnknownCount,
+    const HostField f = host_field(cfg);
+    *out = air_plan(prog, n_insns, widths, n_mats, f.dc, f.p, kAirUnknownCount, kAirUnknownCount,
                     P3R_AIR_MAX_LIVE, AIR_MODE_WITNESS).witness;
   });
 }
@@ -969,12 +949,7 @@ int p3r_witness_program_dmat(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_in
     if (out) *out = nullptr;
     if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
     if (!out) fail(P3R_EINVAL, "out is NULL");
-    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
-    std::vector<const p3r_dmat*> ms(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      ms[i] = mats[i];
-    }
+    const auto ms = checked_mats(mats, n_mats);
     *out = P3R_FIELD_CALL(ctx, witness_program, ctx, prog, n_insns, ms, height, public_values, n_public, challenges, n_challenges).release();
   });
 }
@@ -984,11 +959,8 @@ int p3r_affine_scan_info(const p3r_config* cfg, const p3r_recurrence* recs, size
                          p3r_scan_info* out) {
   return guard(nullptr, [&] {
     if (!cfg || !out) fail(P3R_EINVAL, "NULL argument");
-    if (cfg->field != P3R_FIELD_KOALA_BEAR && cfg->field != P3R_FIELD_BABY_BEAR) fail(P3R_EINVAL, "unknown field %u", cfg->field);
-    if (cfg->challenge_degree != 0 && cfg->challenge_degree != 4 && cfg->challenge_degree != 5)
-      fail(P3R_EINVAL, "challenge_degree must be 4 or 5 (got %u)", cfg->challenge_degree);
-    const uint32_t p = cfg->field == P3R_FIELD_KOALA_BEAR ? KoalaBearParams::P : BabyBearParams::P;
-    *out = scan_plan(recs, n_recs, widths, n_mats, cfg->challenge_degree == 5 ? 5 : 4, p).info;
+    const HostField f = host_field(cfg);
+    *out = scan_plan(recs, n_recs, widths, n_mats, f.dc, f.p).info;
   });
 }
 int p3r_affine_scan_dmat(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs, const p3r_dmat* const* mats, size_t n_mats,
@@ -997,12 +969,7 @@ int p3r_affine_scan_dmat(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs
     if (out) *out = nullptr;
     if (!ctx) fail(P3R_EINVAL, "ctx is NULL");
     if (!out) fail(P3R_EINVAL, "out is NULL");
-    if (n_mats && !mats) fail(P3R_EINVAL, "mats is NULL");
-    std::vector<const p3r_dmat*> ms(n_mats);
-    for (size_t i = 0; i < n_mats; ++i) {
-      if (!mats[i]) fail(P3R_EINVAL, "matrix %zu is NULL", i);
-      ms[i] = mats[i];
-    }
+    const auto ms = checked_mats(mats, n_mats);
     *out = P3R_FIELD_CALL(ctx, affine_scan, ctx, recs, n_recs, ms, last_out).release();
   });
 }

@@ -2,15 +2,17 @@
 // AIR the caller brings as data.  Own translation unit (tu_api.h).  The host half - validation, typing, degrees,
 // liveness, slots, the instruction stream, the per-chunk constants - is air_program.h; the interpreter is
 // k_quotient_program (kernels_air.hip.h).  One launch per call, whatever the program; the call only enqueues.
-// The lookup-program seam (p3r_logup_program_dmat) lives here too: the same host half in its lookup mode, the same
-// interpreter with the lookup sinks (k_logup_program), and the prover's scan for the running sum.
-// So do the two checks of a caller's traces: p3r_check_program_dmat (k_check_program: the constraints on the trace domain,
-// a first failing row and a count per constraint) and p3r_lookup_check_dmat (k_lookup_records, then the stable radix sort
-// and the sums of device_prims.hip.h: the keys of the bus whose multiplicities do not cancel).
-// p3r_lookup_multiplicities_dmat is the same pass (LookupPass) with another end: k_lookup_scatter gives every key's first
-// table slot the sum its queries ask for - the multiplicity column of a table - and reports the keys no table slot offers.
-// The witness seam (p3r_witness_program_dmat) is the interpreter once more, in its witness mode (k_witness_program): the
-// values a program stores become the columns of a new trace.  One launch; the call only enqueues.
+// The seams that run a program on TRACES live here too, all of them k_trace_program with a sink of their own:
+// the lookup-program seam (p3r_logup_program_dmat: the same host half in its lookup mode, LogupProgSink, and the prover's
+// scan for the running sum); the two checks of a caller's traces, p3r_check_program_dmat (CheckProgSink: the constraints
+// on the trace domain, a first failing row and a count per constraint) and p3r_lookup_check_dmat (RecordSink, then the
+// stable radix sort and the sums of device_prims.hip.h: the keys of the bus whose multiplicities do not cancel);
+// p3r_lookup_multiplicities_dmat, the same pass (LookupPass) with another end: k_lookup_scatter gives every key's first
+// table slot the sum its queries ask for - the multiplicity column of a table - and reports the keys no table slot offers;
+// and the witness seam (p3r_witness_program_dmat: the witness mode, WitnessSink): the values a program stores become the
+// columns of a new trace.  One launch; the call only enqueues.
+// What they share is written once: the refusals about tables and matrices, the upload (ProgramBlob) and the launch
+// (launch_program: the grid, the opt-in to a slot file above 48 KiB, the error check).
 // The recurrence seam (p3r_affine_scan_dmat) is the one entry here that runs no program: the accumulator columns
 // s[r + 1] = a[r] s[r] + b[r] of resident traces, validated by scan_plan.h and scanned by k_affine_scan (kernels_scan.hip.h).
 #include <algorithm>
@@ -25,147 +27,69 @@ namespace p3r {
 
 namespace {
 
-template <class PP, int DC>
-std::vector<std::unique_ptr<p3r_dmat>> quotient_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns,
-                                                           const std::vector<const p3r_dmat*>& mats, uint32_t added_bits, uint32_t shift,
-                                                           uint32_t log_q, const uint32_t* publics, size_t n_public,
-                                                           const uint32_t* challenges, size_t n_challenges, const uint32_t* alpha_words) {
-  using F = Fp<PP>;
-  // ---- everything that is refused, before anything is allocated or launched
-  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the constraint-program seam does not serve zk contexts (their quotient domains are doubled)");
-  if (log_q > (uint32_t)kAirMaxLogChunks) fail(P3R_EUNSUPPORTED, "log_quotient_degree > %d is not supported", kAirMaxLogChunks);
-  if (added_bits > 31) fail(P3R_EINVAL, "added_bits (%u) out of range", added_bits);
-  if (added_bits < log_q) fail(P3R_EINVAL, "added_bits (%u) is below log_quotient_degree (%u): the LDEs do not hold the quotient domain", added_bits, log_q);
-  if (mats.empty()) fail(P3R_EINVAL, "n_mats == 0: no trace to evaluate the program on");
-  if (!alpha_words) fail(P3R_EINVAL, "alpha is NULL");
+// ---- what the entries that run a program refuse about its tables and matrices, each written once.  The entries call them
+// in their own order, between refusals of their own: which refusal comes first is part of what an entry promises.
+inline void refuse_null_tables(const uint32_t* publics, size_t n_public, const uint32_t* challenges, size_t n_challenges) {
   if ((n_public && !publics) || (n_challenges && !challenges)) fail(P3R_EINVAL, "public_values or challenges is NULL");
-  const size_t H = mats[0]->h;
-  const int log_H = log2_exact(H, "matrix height");
-  if (log_H > PP::TWO_ADICITY) fail(P3R_EINVAL, "2^%d rows exceed the field's two-adicity (%d)", log_H, PP::TWO_ADICITY);
-  if ((uint32_t)log_H < added_bits) fail(P3R_EINVAL, "a matrix of %zu rows is no LDE of blow-up 2^%u", H, added_bits);
-  std::vector<size_t> widths(mats.size());
-  size_t n_cols = 0;
-  for (size_t m = 0; m < mats.size(); ++m) {
-    if (mats[m]->h != H) fail(P3R_EINVAL, "matrix %zu has %zu rows, matrix 0 has %zu: the traces of one AIR share a height", m, mats[m]->h, H);
-    widths[m] = mats[m]->w;
-    n_cols += widths[m];
-  }
-  if (n_cols > 0x7fffffffu) fail(P3R_EINVAL, "too many columns");
+}
+template <class PP, int DC>
+void refuse_non_canonical(const uint32_t* publics, size_t n_public, const uint32_t* challenges, size_t n_challenges) {
   for (size_t k = 0; k < n_public; ++k)
     if (publics[k] >= PP::P) fail(P3R_EINVAL, "non-canonical public value %zu", k);
   for (size_t k = 0; k < n_challenges * DC; ++k)
     if (challenges[k] >= PP::P) fail(P3R_EINVAL, "non-canonical word %zu of challenge %zu", k % DC, k / DC);
-  for (int k = 0; k < DC; ++k)
-    if (alpha_words[k] >= PP::P) fail(P3R_EINVAL, "non-canonical word %d of alpha", k);
-  const AirPlan plan = air_plan(prog, n_insns, widths.data(), widths.size(), DC, PP::P, n_public, n_challenges, P3R_AIR_MAX_LIVE);
-  if (log_q < plan.info.log_quotient_degree)
-    fail(P3R_EINVAL, "log_quotient_degree %u is below what the program needs (%u: its largest constraint degree is %u)", log_q,
-         plan.info.log_quotient_degree, plan.info.max_degree);
-  const int log_h = log_H - (int)added_bits, log_n = log_h + (int)log_q;
-  const AirDomain dom = air_domain<PP>(shift, log_h, (int)log_q);
-  const size_t lds = plan.lds_bytes(DC);
-  if (lds > kAirMaxLdsBytes) fail(P3R_EUNSUPPORTED, "the program's slot file (%zu bytes) does not fit the LDS", lds);
-
-  // ---- the launch
-  const AirCompiled code = air_compile<PP>(plan, prog, n_insns, widths.data(), widths.size(), DC, publics, challenges);
-  std::vector<const uint32_t*> cols;
-  cols.reserve(n_cols);
-  for (const p3r_dmat* m : mats)
-    for (size_t c = 0; c < m->w; ++c) cols.push_back(m->d + c * m->h);
-  const size_t h = size_t(1) << log_h, n_chunks = size_t(1) << log_q;
-  std::vector<std::unique_ptr<p3r_dmat>> outs;
-  for (size_t c = 0; c < n_chunks; ++c) outs.push_back(dmat_alloc(h, DC));   // [DC][h]: column k is coefficient k
-  // one upload: the per-chunk tables, then the instruction stream, the challenge table and the column pointers
-  const size_t off_insns = (sizeof(AirChunkTables) + 15) / 16 * 16;
-  const size_t off_consts = off_insns + code.insns.size() * sizeof(AirDevInsn);
-  const size_t off_cols = (off_consts + code.ext_consts.size() * 4 + 7) / 8 * 8;
-  std::vector<unsigned char> blob(off_cols + cols.size() * sizeof(void*));
-  DevBuf d_blob((blob.size() + 3) / 4);
-  unsigned char* base = reinterpret_cast<unsigned char*>(d_blob.p);
-  AirProgArgs a{};
-  a.insns = reinterpret_cast<const AirDevInsn*>(base + off_insns);
-  a.ext_consts = reinterpret_cast<const uint32_t*>(base + off_consts);
-  a.cols = reinterpret_cast<const uint32_t* const*>(base + off_cols);
-  a.chunks = reinterpret_cast<const AirChunkTables*>(base);
-  AirChunkTables t{};
-  for (size_t c = 0; c < n_chunks; ++c) {
-    t.zh[c] = dom.zh[c];
-    t.zh_inv[c] = dom.zh_inv[c];
-    t.out[c] = outs[c]->d;
-  }
-  a.n_insns = (uint32_t)code.insns.size();
-  a.log_n = log_n;
-  a.log_q = (int)log_q;
-  a.flags = (plan.uses_x ? 1u : 0u) | (plan.uses_inv ? 2u : 0u);
-  a.shift = dom.shift;
-  a.w_n = dom.w_n;
-  a.g_inv = dom.g_inv;
-  for (int k = 0; k < DC; ++k) a.alpha[k] = F::from_canonical(alpha_words[k]).v;
-  memcpy(blob.data(), &t, sizeof t);
-  memcpy(blob.data() + off_insns, code.insns.data(), code.insns.size() * sizeof(AirDevInsn));
-  if (!code.ext_consts.empty()) memcpy(blob.data() + off_consts, code.ext_consts.data(), code.ext_consts.size() * 4);
-  if (!cols.empty()) memcpy(blob.data() + off_cols, cols.data(), cols.size() * sizeof(void*));
-  P3R_HIP(ctx->stage.upload(ctx->stream, d_blob.p, blob.data(), blob.size()));
-  {
-    ProfScope ps(ctx, "quotient_program");
-    // rows j < N = 2^log_n <= H of every column are read, words k * h + r < DC * h of every chunk written: all inside
-    // the matrices' allocations
-    const unsigned blocks = (unsigned)(((size_t(1) << log_n) + kAirLanes - 1) / kAirLanes);
-    // a slot file above the 48 KiB a kernel gets without asking (the worst P3R_AIR_MAX_LIVE admits is 72 KiB)
-    if (lds > 48 * 1024)
-      P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quotient_program<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kAirMaxLdsBytes));
-    hipLaunchKernelGGL((k_quotient_program<PP, DC>), dim3(blocks), dim3(kAirLanes), lds, ctx->stream,
-                       a);
-  }
-  P3R_HIP(hipGetLastError());
-  // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
-  return outs;
 }
-
-// What the entries that run a program on TRACES (the lookup-program seam and the two checks) refuse about one program
-// and its matrices, in one order for all of them, and what they keep of it: the plan, and the figures of the launch.
+// What an entry keeps of one program and its matrices: the plan, and the figures of the launch.  h and log_h are the height
+// of the MATRICES: of the traces, or in the quotient seam of their LDEs - the trace height there is a local of the entry.
 struct TraceProgram {
   AirPlan plan;
   std::vector<size_t> widths;
   size_t h = 0, n_cols = 0, lds = 0;
   int log_h = 0;
+  // the widths of `mats`, which share the height h; `whose` ("AIR", "table") is how the refusal names them
+  void columns(const std::vector<const p3r_dmat*>& mats, const char* whose) {
+    widths.resize(mats.size());
+    for (size_t m = 0; m < mats.size(); ++m) {
+      if (mats[m]->h != h)
+        fail(P3R_EINVAL, "matrix %zu has %zu rows, matrix 0 has %zu: the traces of one %s share a height", m, mats[m]->h, h, whose);
+      widths[m] = mats[m]->w;
+      n_cols += widths[m];
+    }
+    if (n_cols > 0x7fffffffu) fail(P3R_EINVAL, "too many columns");
+  }
+  // the plan's slot file against the LDS
+  void slot_file(int dc) {
+    lds = plan.lds_bytes(dc);
+    if (lds > kAirMaxLdsBytes) fail(P3R_EUNSUPPORTED, "the program's slot file (%zu bytes) does not fit the LDS", lds);
+  }
 };
+// What the entries that run a program on TRACES (the lookup-program seam, the two checks, the witness seam) refuse, in one
+// order for all of them.
 // `height`: the witness seam's, which takes a program with no input matrix and then needs it; 0 with matrices: theirs.
 template <class PP, int DC>
 TraceProgram trace_program(const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats, const uint32_t* publics,
                            size_t n_public, const uint32_t* challenges, size_t n_challenges, AirMode mode, size_t height = 0) {
   TraceProgram tp;
   if (mats.empty() && mode != AIR_MODE_WITNESS) fail(P3R_EINVAL, "n_mats == 0: no trace to evaluate the program on");
-  if ((n_public && !publics) || (n_challenges && !challenges)) fail(P3R_EINVAL, "public_values or challenges is NULL");
+  refuse_null_tables(publics, n_public, challenges, n_challenges);
   const size_t h = tp.h = mats.empty() ? height : mats[0]->h;
   if (!mats.empty() && height && height != h)
     fail(P3R_EINVAL, "height (%zu) is not the matrices' (%zu): pass 0, or the height of the traces", height, h);
   tp.log_h = air_trace_log_height(h, PP::TWO_ADICITY);   // a power of two within the field's two-adicity
-  tp.widths.resize(mats.size());
-  for (size_t m = 0; m < mats.size(); ++m) {
-    if (mats[m]->h != h) fail(P3R_EINVAL, "matrix %zu has %zu rows, matrix 0 has %zu: the traces of one table share a height", m, mats[m]->h, h);
-    tp.widths[m] = mats[m]->w;
-    tp.n_cols += tp.widths[m];
-  }
-  if (tp.n_cols > 0x7fffffffu) fail(P3R_EINVAL, "too many columns");
-  for (size_t k = 0; k < n_public; ++k)
-    if (publics[k] >= PP::P) fail(P3R_EINVAL, "non-canonical public value %zu", k);
-  for (size_t k = 0; k < n_challenges * DC; ++k)
-    if (challenges[k] >= PP::P) fail(P3R_EINVAL, "non-canonical word %zu of challenge %zu", k % DC, k / DC);
+  tp.columns(mats, "table");
+  refuse_non_canonical<PP, DC>(publics, n_public, challenges, n_challenges);
   tp.plan = air_plan(prog, n_insns, tp.widths.data(), tp.widths.size(), DC, PP::P, n_public, n_challenges, P3R_AIR_MAX_LIVE, mode);
-  tp.lds = tp.plan.lds_bytes(DC);
-  if (tp.lds > kAirMaxLdsBytes) fail(P3R_EUNSUPPORTED, "the program's slot file (%zu bytes) does not fit the LDS", tp.lds);
+  tp.slot_file(DC);
   return tp;
 }
 
-// The instruction stream, the challenge table and the column pointers of one launch as one upload, after `head` bytes the
-// caller fills (answer words, a job): where each part lies in the blob.
+// The one place that knows the upload of a launch: `head` bytes the caller fills (answer words, a job, the chunk tables),
+// then the instruction stream (16-aligned), the challenge table and the column pointers (8-aligned).
 struct ProgramBlob {
-  size_t off_insns, off_consts, off_cols;
+  size_t off_insns, off_consts, off_cols, n_insns;
   std::vector<unsigned char> host;
   DevBuf dev;
-  ProgramBlob(size_t head, const AirCompiled& code, const std::vector<const p3r_dmat*>& mats, size_t n_cols) {
+  ProgramBlob(size_t head, const AirCompiled& code, const std::vector<const p3r_dmat*>& mats, size_t n_cols) : n_insns(code.insns.size()) {
     std::vector<const uint32_t*> cols;
     cols.reserve(n_cols);
     for (const p3r_dmat* m : mats)
@@ -180,16 +104,93 @@ struct ProgramBlob {
     dev.alloc((host.size() + 3) / 4);
   }
   unsigned char* base() const { return reinterpret_cast<unsigned char*>(dev.p); }
-  const AirDevInsn* insns() const { return reinterpret_cast<const AirDevInsn*>(base() + off_insns); }
-  const uint32_t* ext_consts() const { return reinterpret_cast<const uint32_t*>(base() + off_consts); }
-  const uint32_t* const* cols() const { return reinterpret_cast<const uint32_t* const*>(base() + off_cols); }
+  AirStream stream() const {
+    return AirStream{reinterpret_cast<const AirDevInsn*>(base() + off_insns), reinterpret_cast<const uint32_t*>(base() + off_consts),
+                     reinterpret_cast<const uint32_t* const*>(base() + off_cols), (uint32_t)n_insns};
+  }
+  // the blob goes back to the context's pool when it dies; the pool is ordered by the stream the launch is on (context.h)
   void upload(p3r_ctx* ctx) { P3R_HIP(ctx->stage.upload(ctx->stream, dev.p, host.data(), host.size())); }
 };
 
+// One launch of an interpreter: one lane per row, one wave per workgroup, `lds` bytes of slot file.  Above the 48 KiB a
+// kernel gets without asking (the worst P3R_AIR_MAX_LIVE admits is 72 KiB) the kernel is opted in, every time.
+template <class Args>
+void launch_program(p3r_ctx* ctx, void (*kernel)(Args), size_t n_rows, size_t lds, const Args& a) {
+  const unsigned blocks = (unsigned)((n_rows + kAirLanes - 1) / kAirLanes);
+  if (lds > 48 * 1024)
+    P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAirMaxLdsBytes));
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kAirLanes), lds, ctx->stream, a);
+  P3R_HIP(hipGetLastError());
+}
+
+template <class PP, int DC>
+std::vector<std::unique_ptr<p3r_dmat>> quotient_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns,
+                                                           const std::vector<const p3r_dmat*>& mats, uint32_t added_bits, uint32_t shift,
+                                                           uint32_t log_q, const uint32_t* publics, size_t n_public,
+                                                           const uint32_t* challenges, size_t n_challenges, const uint32_t* alpha_words) {
+  using F = Fp<PP>;
+  // ---- everything that is refused, before anything is allocated or launched
+  if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the constraint-program seam does not serve zk contexts (their quotient domains are doubled)");
+  if (log_q > (uint32_t)kAirMaxLogChunks) fail(P3R_EUNSUPPORTED, "log_quotient_degree > %d is not supported", kAirMaxLogChunks);
+  if (added_bits > 31) fail(P3R_EINVAL, "added_bits (%u) out of range", added_bits);
+  if (added_bits < log_q) fail(P3R_EINVAL, "added_bits (%u) is below log_quotient_degree (%u): the LDEs do not hold the quotient domain", added_bits, log_q);
+  if (mats.empty()) fail(P3R_EINVAL, "n_mats == 0: no trace to evaluate the program on");
+  if (!alpha_words) fail(P3R_EINVAL, "alpha is NULL");
+  refuse_null_tables(publics, n_public, challenges, n_challenges);
+  TraceProgram tp;   // of the LDEs: tp.h and tp.log_h are their height H; h and log_h below are the trace's
+  const size_t H = tp.h = mats[0]->h;
+  const int log_H = log2_exact(H, "matrix height");
+  if (log_H > PP::TWO_ADICITY) fail(P3R_EINVAL, "2^%d rows exceed the field's two-adicity (%d)", log_H, PP::TWO_ADICITY);
+  if ((uint32_t)log_H < added_bits) fail(P3R_EINVAL, "a matrix of %zu rows is no LDE of blow-up 2^%u", H, added_bits);
+  tp.log_h = log_H;
+  tp.columns(mats, "AIR");
+  refuse_non_canonical<PP, DC>(publics, n_public, challenges, n_challenges);
+  for (int k = 0; k < DC; ++k)
+    if (alpha_words[k] >= PP::P) fail(P3R_EINVAL, "non-canonical word %d of alpha", k);
+  tp.plan = air_plan(prog, n_insns, tp.widths.data(), tp.widths.size(), DC, PP::P, n_public, n_challenges, P3R_AIR_MAX_LIVE);
+  const AirPlan& plan = tp.plan;
+  if (log_q < plan.info.log_quotient_degree)
+    fail(P3R_EINVAL, "log_quotient_degree %u is below what the program needs (%u: its largest constraint degree is %u)", log_q,
+         plan.info.log_quotient_degree, plan.info.max_degree);
+  const int log_h = log_H - (int)added_bits, log_n = log_h + (int)log_q;
+  const AirDomain dom = air_domain<PP>(shift, log_h, (int)log_q);
+  tp.slot_file(DC);
+
+  // ---- the launch
+  const AirCompiled code = air_compile<PP>(plan, prog, n_insns, tp.widths.data(), tp.widths.size(), DC, publics, challenges);
+  const size_t h = size_t(1) << log_h, n_chunks = size_t(1) << log_q;
+  std::vector<std::unique_ptr<p3r_dmat>> outs;
+  for (size_t c = 0; c < n_chunks; ++c) outs.push_back(dmat_alloc(h, DC));   // [DC][h]: column k is coefficient k
+  AirChunkTables t{};   // leads the upload
+  for (size_t c = 0; c < n_chunks; ++c) {
+    t.zh[c] = dom.zh[c];
+    t.zh_inv[c] = dom.zh_inv[c];
+    t.out[c] = outs[c]->d;
+  }
+  ProgramBlob blob(sizeof t, code, mats, tp.n_cols);
+  memcpy(blob.host.data(), &t, sizeof t);
+  blob.upload(ctx);
+  AirProgArgs a{};
+  a.prog = blob.stream();
+  a.chunks = reinterpret_cast<const AirChunkTables*>(blob.base());
+  a.log_n = log_n;
+  a.log_q = (int)log_q;
+  a.flags = (plan.uses_x ? 1u : 0u) | (plan.uses_inv ? 2u : 0u);
+  a.shift = dom.shift;
+  a.w_n = dom.w_n;
+  a.g_inv = dom.g_inv;
+  for (int k = 0; k < DC; ++k) a.alpha[k] = F::from_canonical(alpha_words[k]).v;
+  ProfScope ps(ctx, "quotient_program");
+  // rows j < N = 2^log_n <= H of every column are read, words k * h + r < DC * h of every chunk written: all inside
+  // the matrices' allocations
+  launch_program(ctx, k_quotient_program<PP, DC>, size_t(1) << log_n, tp.lds, a);
+  return outs;
+}
+
 // The lookup-program seam (p3r_logup_program_dmat): the LogUp gadget of p3_lookup for interactions the caller brings as
-// data.  k_logup_program writes the fraction columns and each row's total; the running sum and the table's sum are the
-// prover's own three-mode scan k_ef_scan over a LogupJob of one job.  The call waits for the stream: the sum goes to the
-// caller's challenger, and with it comes the word that says whether a denominator vanished.
+// data.  k_trace_program with the LogUp sink writes the fraction columns and each row's total; the running sum and the
+// table's sum are the prover's own three-mode scan k_ef_scan over a LogupJob of one job.  The call waits for the stream: the
+// sum goes to the caller's challenger, and with it comes the word that says whether a denominator vanished.
 template <class PP, int DC>
 std::unique_ptr<p3r_dmat> logup_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
                                            const uint32_t* publics, size_t n_public, const uint32_t* challenges, size_t n_challenges,
@@ -199,41 +200,24 @@ std::unique_ptr<p3r_dmat> logup_program_dc(p3r_ctx* ctx, const p3r_air_insn* pro
   if (ctx->cfg.zk) fail(P3R_EUNSUPPORTED, "the lookup-program seam does not serve zk contexts (their traces are randomised and their domains doubled)");
   if (!sum_out) fail(P3R_EINVAL, "sum_out is NULL");
   const TraceProgram tp = trace_program<PP, DC>(prog, n_insns, mats, publics, n_public, challenges, n_challenges, AIR_MODE_LOOKUP);
-  const AirPlan& plan = tp.plan;
-  const std::vector<size_t>& widths = tp.widths;
-  const size_t h = tp.h, n_cols = tp.n_cols, lds = tp.lds;
-  const int log_h = tp.log_h;
-  const size_t G = plan.lookup.n_columns;
+  const size_t h = tp.h, G = tp.plan.lookup.n_columns;
   if (G > (0x7fffffffu / DC) - 1) fail(P3R_EINVAL, "too many auxiliary columns");
 
   // ---- the launches
-  const AirCompiled code = air_compile<PP>(plan, prog, n_insns, widths.data(), widths.size(), DC, publics, challenges);
-  std::vector<const uint32_t*> cols;
-  cols.reserve(n_cols);
-  for (const p3r_dmat* m : mats)
-    for (size_t c = 0; c < m->w; ++c) cols.push_back(m->d + c * m->h);
+  const AirCompiled code = air_compile<PP>(tp.plan, prog, n_insns, tp.widths.data(), tp.widths.size(), DC, publics, challenges);
   std::unique_ptr<p3r_dmat> out = dmat_alloc(h, (size_t)DC * (1 + G));   // [DC * (1 + G)][h]
   const size_t n_tiles = (h + kScanTile - 1) / kScanTile;
   DevBuf rowsum((size_t)DC * h), agg((size_t)DC * n_tiles);
-  // one upload: the scan's job, the words the device answers in (bad row, then the table's sum), the instruction stream,
-  // the challenge table and the column pointers
+  // the upload is led by the scan's job and the words the device answers in: the bad row, then the table's sum
   const size_t off_answer = (sizeof(LogupJob) + 15) / 16 * 16;
-  const size_t off_insns = off_answer + 16 * ((4 * (1 + DC) + 15) / 16);
-  const size_t off_consts = off_insns + code.insns.size() * sizeof(AirDevInsn);
-  const size_t off_cols = (off_consts + code.ext_consts.size() * 4 + 7) / 8 * 8;
-  std::vector<unsigned char> blob(off_cols + cols.size() * sizeof(void*));
-  DevBuf d_blob((blob.size() + 3) / 4);
-  unsigned char* base = reinterpret_cast<unsigned char*>(d_blob.p);
-  uint32_t* d_answer = reinterpret_cast<uint32_t*>(base + off_answer);
+  ProgramBlob blob(off_answer + 16 * ((4 * (1 + DC) + 15) / 16), code, mats, tp.n_cols);
+  uint32_t* d_answer = reinterpret_cast<uint32_t*>(blob.base() + off_answer);
   AirLogupArgs a{};
-  a.insns = reinterpret_cast<const AirDevInsn*>(base + off_insns);
-  a.ext_consts = reinterpret_cast<const uint32_t*>(base + off_consts);
-  a.cols = reinterpret_cast<const uint32_t* const*>(base + off_cols);
+  a.prog = blob.stream();
+  a.log_h = tp.log_h;
   a.out = out->d;
   a.rowsum = rowsum.p;
   a.bad_row = d_answer;
-  a.n_insns = (uint32_t)code.insns.size();
-  a.log_h = log_h;
   LogupJob job{};   // what k_ef_scan reads of it
   job.aux = out->d;
   job.rowsum = rowsum.p;
@@ -242,24 +226,17 @@ std::unique_ptr<p3r_dmat> logup_program_dc(p3r_ctx* ctx, const p3r_air_insn* pro
   job.n = h;
   job.n_tiles = (uint32_t)n_tiles;
   const uint32_t answer0[1 + kMaxAirDC] = {0xffffffffu};   // no bad row; the sum is written by the scan
-  memcpy(blob.data(), &job, sizeof job);
-  memcpy(blob.data() + off_answer, answer0, 4 * (1 + DC));
-  memcpy(blob.data() + off_insns, code.insns.data(), code.insns.size() * sizeof(AirDevInsn));
-  if (!code.ext_consts.empty()) memcpy(blob.data() + off_consts, code.ext_consts.data(), code.ext_consts.size() * 4);
-  if (!cols.empty()) memcpy(blob.data() + off_cols, cols.data(), cols.size() * sizeof(void*));
-  P3R_HIP(ctx->stage.upload(ctx->stream, d_blob.p, blob.data(), blob.size()));
+  memcpy(blob.host.data(), &job, sizeof job);
+  memcpy(blob.host.data() + off_answer, answer0, 4 * (1 + DC));
+  blob.upload(ctx);
   {
     ProfScope ps(ctx, "logup_program");
     // rows r < h of every input column are read; words (col * DC + k) * h + r with 1 <= col <= G, so below
-    // DC * (1 + G) * h, of the output and k * h + r < DC * h of rowsum are written by k_logup_program; k_ef_scan writes
+    // DC * (1 + G) * h, of the output and k * h + r < DC * h of rowsum are written by the interpreter; k_ef_scan writes
     // words k * h + r < DC * h of the output, DC * tile + k < DC * n_tiles of agg and the DC words of the sum: all inside
     // the allocations above
-    const unsigned blocks = (unsigned)((h + kAirLanes - 1) / kAirLanes);
-    if (lds > 48 * 1024)
-      P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_logup_program<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kAirMaxLdsBytes));
-    hipLaunchKernelGGL((k_logup_program<PP, DC>), dim3(blocks), dim3(kAirLanes), lds, ctx->stream, a);
-    const auto* d_job = reinterpret_cast<const LogupJob*>(base);
+    launch_program(ctx, k_trace_program<PP, DC, LogupProgSink>, h, tp.lds, a);
+    const auto* d_job = reinterpret_cast<const LogupJob*>(blob.base());
     hipLaunchKernelGGL((k_ef_scan<PP, DC>), dim3((unsigned)n_tiles), dim3(kBlock), 0, ctx->stream, 0, d_job, 1);
     hipLaunchKernelGGL((k_ef_scan<PP, DC>), dim3(1), dim3(kBlock), 0, ctx->stream, 1, d_job, 1);
     hipLaunchKernelGGL((k_ef_scan<PP, DC>), dim3((unsigned)n_tiles), dim3(kBlock), 0, ctx->stream, 2, d_job, 1);
@@ -273,7 +250,7 @@ std::unique_ptr<p3r_dmat> logup_program_dc(p3r_ctx* ctx, const p3r_air_insn* pro
 }
 
 // The witness seam (p3r_witness_program_dmat): the values a witness program stores, as the columns of a fresh trace.  One
-// launch of k_witness_program; nothing is read back and the call does not wait.
+// launch of k_trace_program with the witness sink; nothing is read back and the call does not wait.
 template <class PP, int DC>
 std::unique_ptr<p3r_dmat> witness_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
                                              size_t height, const uint32_t* publics, size_t n_public, const uint32_t* challenges,
@@ -289,25 +266,14 @@ std::unique_ptr<p3r_dmat> witness_program_dc(p3r_ctx* ctx, const p3r_air_insn* p
   ProgramBlob blob(0, code, mats, tp.n_cols);
   blob.upload(ctx);
   AirWitnessArgs a{};
-  a.insns = blob.insns();
-  a.ext_consts = blob.ext_consts();
-  a.cols = blob.cols();
-  a.out = out->d;
-  a.n_insns = (uint32_t)code.insns.size();
+  a.prog = blob.stream();
   a.log_h = tp.log_h;
-  {
-    ProfScope ps(ctx, "witness_program");
-    // rows r < h of every input column are read (with no input matrix the stream has no load); a STORE writes words
-    // col * h + r with col < W - air_plan took W as one past the highest stored column - and r < h: all inside the
-    // allocation above.  Every column below W is stored: nothing of the output stays uninitialised.
-    const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
-    if (tp.lds > 48 * 1024)
-      P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_witness_program<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kAirMaxLdsBytes));
-    hipLaunchKernelGGL((k_witness_program<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, ctx->stream, a);
-  }
-  P3R_HIP(hipGetLastError());
-  // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
+  a.out = out->d;
+  ProfScope ps(ctx, "witness_program");
+  // rows r < h of every input column are read (with no input matrix the stream has no load); a STORE writes words
+  // col * h + r with col < W - air_plan took W as one past the highest stored column - and r < h: all inside the
+  // allocation above.  Every column below W is stored: nothing of the output stays uninitialised.
+  launch_program(ctx, k_trace_program<PP, DC, WitnessSink>, tp.h, tp.lds, a);
   return out;
 }
 
@@ -376,7 +342,7 @@ std::unique_ptr<p3r_dmat> affine_scan_dc(p3r_ctx* ctx, const p3r_recurrence* rec
 }
 
 // The constraint check (p3r_check_program_dmat): DebugConstraintBuilder / check_air_satisfies for constraints the caller
-// brings as data.  One launch of k_check_program; the device answers with a first failing row and a count per constraint,
+// brings as data.  One launch of k_trace_program<CheckProgSink>; the device answers with a first failing row and a count per constraint,
 // from which the report is derived here.  A trace that fails is a result, not an error.  Waits for the stream.
 template <class PP, int DC>
 void check_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
@@ -395,24 +361,16 @@ void check_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, co
   memset(blob.host.data() + 8 * nc, 0xff, 4 * nc);
   blob.upload(ctx);
   AirCheckArgs a{};
-  a.insns = blob.insns();
-  a.ext_consts = blob.ext_consts();
-  a.cols = blob.cols();
+  a.prog = blob.stream();
+  a.log_h = tp.log_h;
   a.n_failed = reinterpret_cast<unsigned long long*>(blob.base());
   a.first_row = blob.dev.p + 2 * nc;
-  a.n_insns = (uint32_t)code.insns.size();
-  a.log_h = tp.log_h;
   {
     ProfScope ps(ctx, "check_program");
     // rows r < h of every input column are read; constraint k < nc - the ASSERTs of the stream, which air_plan counted -
     // touches n_failed[k] and first_row[k]: all inside the allocations above
-    const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
-    if (tp.lds > 48 * 1024)
-      P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_check_program<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kAirMaxLdsBytes));
-    hipLaunchKernelGGL((k_check_program<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, ctx->stream, a);
+    launch_program(ctx, k_trace_program<PP, DC, CheckProgSink>, tp.h, tp.lds, a);
   }
-  P3R_HIP(hipGetLastError());
   std::vector<uint32_t> answer(3 * nc);
   P3R_HIP(fetch_small(ctx, blob.dev.p, answer.size(), answer.data()));   // waits for the stream
   *report = p3r_check_report{0, 0xffffffffu, 0xffffffffu};
@@ -431,7 +389,7 @@ void check_program_dc(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, co
 
 // ---- the lookup check (p3r_lookup_check_dmat): p3_lookup::debug_util::check_lookups over lookup programs.
 // Slots: term t of row r of instance p is slot base_p + r * n_terms_p + t; a slot whose multiplicity is not zero is a
-// record, and ascending slots are record order.  After k_lookup_records the pass is the primitives of
+// record, and ascending slots are record order.  After k_trace_program<RecordSink> the pass is the primitives of
 // device_prims.hip.h and the few kernels below, which index by what those wrote.
 
 // words [DC][n_slots] of the records at sorted positions i - 1 and i differ: i opens a key's run
@@ -576,27 +534,18 @@ struct LookupPass {
         ProgramBlob blob(0, code, in.mats, tp.n_cols);
         blob.upload(ctx);
         AirRecordArgs a{};
-        a.insns = blob.insns();
-        a.ext_consts = blob.ext_consts();
-        a.cols = blob.cols();
+        a.prog = blob.stream();
+        a.log_h = tp.log_h;
         a.den = den.p;
         a.mul = mul.p;
         a.mark = mark.p;
         a.n_slots = S;
         a.base = base[p];
         a.n_terms = tp.plan.lookup.n_terms;
-        a.n_insns = (uint32_t)code.insns.size();
-        a.log_h = tp.log_h;
         // rows r < h of every input column are read; slot base + r * n_terms + t with r < h and t < n_terms - the TERMs of
         // the stream, which air_plan counted - lies in [base_p, base_p+1), so below S: words k * S + slot < DC * S of den and
         // mul and word slot of mark.  Every slot of the instance is written: nothing is read uninitialised afterwards.
-        const unsigned blocks = (unsigned)((tp.h + kAirLanes - 1) / kAirLanes);
-        if (tp.lds > 48 * 1024)
-          P3R_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lookup_records<PP, DC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kAirMaxLdsBytes));
-        hipLaunchKernelGGL((k_lookup_records<PP, DC>), dim3(blocks), dim3(kAirLanes), tp.lds, s, a);
-        P3R_HIP(hipGetLastError());
-        // the blob goes back to the context's pool, which is ordered by the stream the launch is on (context.h)
+        launch_program(ctx, k_trace_program<PP, DC, RecordSink>, tp.h, tp.lds, a);
       }
     }
     {
@@ -799,11 +748,9 @@ template <class PP>
 std::unique_ptr<p3r_dmat> logup_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
                                         const uint32_t* publics, size_t n_public, const uint32_t* challenges, size_t n_challenges,
                                         uint32_t* sum_out) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return logup_program_dc<PP, 5>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, sum_out);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return logup_program_dc<PP, 4>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, sum_out);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) {
+    return logup_program_dc<PP, decltype(dc)::value>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, sum_out);
+  });
 }
 
 template <class PP>
@@ -811,104 +758,69 @@ std::vector<std::unique_ptr<p3r_dmat>> quotient_program(p3r_ctx* ctx, const p3r_
                                                         const std::vector<const p3r_dmat*>& mats, uint32_t added_bits, uint32_t shift,
                                                         uint32_t log_quotient_degree, const uint32_t* publics, size_t n_public,
                                                         const uint32_t* challenges, size_t n_challenges, const uint32_t* alpha) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>)
-      return quotient_program_dc<PP, 5>(ctx, prog, n_insns, mats, added_bits, shift, log_quotient_degree, publics, n_public, challenges,
-                                        n_challenges, alpha);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return quotient_program_dc<PP, 4>(ctx, prog, n_insns, mats, added_bits, shift, log_quotient_degree, publics, n_public, challenges,
-                                    n_challenges, alpha);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) {
+    return quotient_program_dc<PP, decltype(dc)::value>(ctx, prog, n_insns, mats, added_bits, shift, log_quotient_degree, publics, n_public,
+                                                        challenges, n_challenges, alpha);
+  });
 }
 
 template <class PP>
 void check_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats, const uint32_t* publics,
                    size_t n_public, const uint32_t* challenges, size_t n_challenges, p3r_check_report* report, uint32_t* first_row_out,
                    uint64_t* n_failed_out) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>)
-      return check_program_dc<PP, 5>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, report, first_row_out, n_failed_out);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  check_program_dc<PP, 4>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, report, first_row_out, n_failed_out);
+  with_challenge_degree<PP>(ctx, [&](auto dc) {
+    check_program_dc<PP, decltype(dc)::value>(ctx, prog, n_insns, mats, publics, n_public, challenges, n_challenges, report, first_row_out,
+                                              n_failed_out);
+  });
 }
 
 template <class PP>
 void lookup_check(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges, size_t n_challenges,
                   p3r_lookup_imbalance* out, size_t cap, uint64_t* n_unbalanced_out) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return lookup_check_dc<PP, 5>(ctx, insts, challenges, n_challenges, out, cap, n_unbalanced_out);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  lookup_check_dc<PP, 4>(ctx, insts, challenges, n_challenges, out, cap, n_unbalanced_out);
+  with_challenge_degree<PP>(ctx, [&](auto dc) { lookup_check_dc<PP, decltype(dc)::value>(ctx, insts, challenges, n_challenges, out, cap, n_unbalanced_out); });
 }
 
 template <class PP>
 std::unique_ptr<p3r_dmat> lookup_multiplicities(p3r_ctx* ctx, const std::vector<LookupCheckInstance>& insts, const uint32_t* challenges,
                                                 size_t n_challenges, p3r_lookup_imbalance* missing, size_t cap, uint64_t* n_missing_out) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return lookup_multiplicities_dc<PP, 5>(ctx, insts, challenges, n_challenges, missing, cap, n_missing_out);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return lookup_multiplicities_dc<PP, 4>(ctx, insts, challenges, n_challenges, missing, cap, n_missing_out);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) {
+    return lookup_multiplicities_dc<PP, decltype(dc)::value>(ctx, insts, challenges, n_challenges, missing, cap, n_missing_out);
+  });
 }
 
 template <class PP>
 std::unique_ptr<p3r_dmat> witness_program(p3r_ctx* ctx, const p3r_air_insn* prog, size_t n_insns, const std::vector<const p3r_dmat*>& mats,
                                           size_t height, const uint32_t* publics, size_t n_public, const uint32_t* challenges,
                                           size_t n_challenges) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return witness_program_dc<PP, 5>(ctx, prog, n_insns, mats, height, publics, n_public, challenges, n_challenges);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return witness_program_dc<PP, 4>(ctx, prog, n_insns, mats, height, publics, n_public, challenges, n_challenges);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) {
+    return witness_program_dc<PP, decltype(dc)::value>(ctx, prog, n_insns, mats, height, publics, n_public, challenges, n_challenges);
+  });
 }
 
 template <class PP>
 std::unique_ptr<p3r_dmat> affine_scan(p3r_ctx* ctx, const p3r_recurrence* recs, size_t n_recs, const std::vector<const p3r_dmat*>& mats,
                                       uint32_t* last_out) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return affine_scan_dc<PP, 5>(ctx, recs, n_recs, mats, last_out);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return affine_scan_dc<PP, 4>(ctx, recs, n_recs, mats, last_out);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) { return affine_scan_dc<PP, decltype(dc)::value>(ctx, recs, n_recs, mats, last_out); });
 }
 
-#define P3R_AIR_INSTANCE(PP)                                                                                                     \
-  template std::vector<std::unique_ptr<p3r_dmat>> quotient_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t,                    \
-                                                                       const std::vector<const p3r_dmat*>&, uint32_t, uint32_t, \
-                                                                       uint32_t, const uint32_t*, size_t, const uint32_t*, size_t, \
-                                                                       const uint32_t*);
+#define P3R_AIR_INSTANCE(PP)                                                                                                               \
+  template std::vector<std::unique_ptr<p3r_dmat>> quotient_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t,                              \
+                                                                       const std::vector<const p3r_dmat*>&, uint32_t, uint32_t, uint32_t,  \
+                                                                       const uint32_t*, size_t, const uint32_t*, size_t, const uint32_t*); \
+  template std::unique_ptr<p3r_dmat> logup_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&,         \
+                                                       const uint32_t*, size_t, const uint32_t*, size_t, uint32_t*);                       \
+  template void check_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&, const uint32_t*, size_t,     \
+                                  const uint32_t*, size_t, p3r_check_report*, uint32_t*, uint64_t*);                                       \
+  template void lookup_check<PP>(p3r_ctx*, const std::vector<LookupCheckInstance>&, const uint32_t*, size_t, p3r_lookup_imbalance*,        \
+                                 size_t, uint64_t*);                                                                                       \
+  template std::unique_ptr<p3r_dmat> lookup_multiplicities<PP>(p3r_ctx*, const std::vector<LookupCheckInstance>&, const uint32_t*, size_t, \
+                                                               p3r_lookup_imbalance*, size_t, uint64_t*);                                  \
+  template std::unique_ptr<p3r_dmat> witness_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&,       \
+                                                         size_t, const uint32_t*, size_t, const uint32_t*, size_t);                        \
+  template std::unique_ptr<p3r_dmat> affine_scan<PP>(p3r_ctx*, const p3r_recurrence*, size_t, const std::vector<const p3r_dmat*>&,         \
+                                                     uint32_t*);
 P3R_AIR_INSTANCE(KoalaBearParams)
 P3R_AIR_INSTANCE(BabyBearParams)
 #undef P3R_AIR_INSTANCE
-#define P3R_LOGUP_INSTANCE(PP)                                                                                                              \
-  template std::unique_ptr<p3r_dmat> logup_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&,          \
-                                                       const uint32_t*, size_t, const uint32_t*, size_t, uint32_t*);
-P3R_LOGUP_INSTANCE(KoalaBearParams)
-P3R_LOGUP_INSTANCE(BabyBearParams)
-#undef P3R_LOGUP_INSTANCE
-#define P3R_CHECK_INSTANCE(PP)                                                                                                            \
-  template void check_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&, const uint32_t*, size_t,    \
-                                  const uint32_t*, size_t, p3r_check_report*, uint32_t*, uint64_t*);                                      \
-  template void lookup_check<PP>(p3r_ctx*, const std::vector<LookupCheckInstance>&, const uint32_t*, size_t, p3r_lookup_imbalance*,        \
-                                 size_t, uint64_t*);                                                                                      \
-  template std::unique_ptr<p3r_dmat> lookup_multiplicities<PP>(p3r_ctx*, const std::vector<LookupCheckInstance>&, const uint32_t*, size_t, \
-                                                               p3r_lookup_imbalance*, size_t, uint64_t*);
-P3R_CHECK_INSTANCE(KoalaBearParams)
-P3R_CHECK_INSTANCE(BabyBearParams)
-#undef P3R_CHECK_INSTANCE
-#define P3R_WITNESS_INSTANCE(PP)                                                                                                       \
-  template std::unique_ptr<p3r_dmat> witness_program<PP>(p3r_ctx*, const p3r_air_insn*, size_t, const std::vector<const p3r_dmat*>&,   \
-                                                         size_t, const uint32_t*, size_t, const uint32_t*, size_t);
-P3R_WITNESS_INSTANCE(KoalaBearParams)
-P3R_WITNESS_INSTANCE(BabyBearParams)
-#undef P3R_WITNESS_INSTANCE
-#define P3R_SCAN_INSTANCE(PP)                                                                                                       \
-  template std::unique_ptr<p3r_dmat> affine_scan<PP>(p3r_ctx*, const p3r_recurrence*, size_t, const std::vector<const p3r_dmat*>&,  \
-                                                     uint32_t*);
-P3R_SCAN_INSTANCE(KoalaBearParams)
-P3R_SCAN_INSTANCE(BabyBearParams)
-#undef P3R_SCAN_INSTANCE
 
 }  // namespace p3r

@@ -7,7 +7,7 @@
 // kernels of kernels_open.hip.h with the seam's entry point), tu_fri.hip (the reduced openings and the fold at the public
 // FRI seam and the commit-phase leaf view: kernels_fri_points.hip.h, and its own instances of k_fri_inv_points, k_fri_vsum
 // and k_fri_fold), tu_air.hip (the constraint-program and lookup-program seams: the interpreters k_quotient_program and
-// k_logup_program of kernels_air.hip.h over the plan and instruction stream of air_program.h),
+// k_trace_program of kernels_air.hip.h over the plan and instruction stream of air_program.h),
 // prep_device.hip.
 // Kernels never call across units; only these host entry points do.
 #pragma once
@@ -42,6 +42,17 @@ inline const void* const_table(p3r_ctx* ctx, const void* data, size_t bytes) {
 }
 inline const uint32_t* const* col_table(p3r_ctx* ctx, const std::vector<const uint32_t*>& cols) {
   return static_cast<const uint32_t* const*>(const_table(ctx, cols.data(), cols.size() * sizeof(void*)));
+}
+
+// The context's challenge degree as a compile-time constant: fn(std::integral_constant<int, 4>) or <int, 5>, the quintic
+// degree refused over BabyBear.  What the entries of the public seams open with.
+template <class PP, class Fn>
+inline decltype(auto) with_challenge_degree(const p3r_ctx* ctx, Fn&& fn) {
+  if (ctx->cfg.challenge_degree == 5) {
+    if constexpr (kHasQuintic<PP>) return fn(std::integral_constant<int, 5>{});
+    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
+  }
+  return fn(std::integral_constant<int, 4>{});
 }
 
 // K5 for a batch of matrices (tu_lde.hip).  in: h x w evaluations over the subgroup (natural order, column-major

@@ -269,28 +269,16 @@ std::unique_ptr<p3r_dmat> fri_leaf_view_dc(p3r_ctx* ctx, const p3r_dmat* vec, ui
 template <class PP>
 std::vector<std::unique_ptr<p3r_dmat>> fri_reduce(p3r_ctx* ctx, const std::vector<FriReduceItem>& items, uint32_t shift,
                                                   const uint32_t* points, const uint32_t* values, const uint32_t* alpha) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return fri_reduce_dc<PP, 5>(ctx, items, shift, points, values, alpha);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return fri_reduce_dc<PP, 4>(ctx, items, shift, points, values, alpha);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) { return fri_reduce_dc<PP, decltype(dc)::value>(ctx, items, shift, points, values, alpha); });
 }
 template <class PP>
 std::unique_ptr<p3r_dmat> fri_fold(p3r_ctx* ctx, const p3r_dmat* in, uint32_t log_arity, const uint32_t* beta, const p3r_dmat* roll_in) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return fri_fold_dc<PP, 5>(ctx, in, log_arity, beta, roll_in);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return fri_fold_dc<PP, 4>(ctx, in, log_arity, beta, roll_in);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) { return fri_fold_dc<PP, decltype(dc)::value>(ctx, in, log_arity, beta, roll_in); });
 }
 
 template <class PP>
 std::unique_ptr<p3r_dmat> fri_leaf_view(p3r_ctx* ctx, const p3r_dmat* vec, uint32_t log_arity) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) return fri_leaf_view_dc<PP, 5>(ctx, vec, log_arity);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-  }
-  return fri_leaf_view_dc<PP, 4>(ctx, vec, log_arity);
+  return with_challenge_degree<PP>(ctx, [&](auto dc) { return fri_leaf_view_dc<PP, decltype(dc)::value>(ctx, vec, log_arity); });
 }
 
 template std::vector<std::unique_ptr<p3r_dmat>> fri_reduce<KoalaBearParams>(p3r_ctx*, const std::vector<FriReduceItem>&, uint32_t,

@@ -85,12 +85,7 @@ void open_points_dc(p3r_ctx* ctx, const std::vector<OpenPointsItem>& items, int 
 template <class PP>
 void open_points(p3r_ctx* ctx, const std::vector<OpenPointsItem>& items, int added_bits, uint32_t shift, bool bit_reversed,
                  const uint32_t* points, uint32_t* values_out) {
-  if (ctx->cfg.challenge_degree == 5) {
-    if constexpr (kHasQuintic<PP>) open_points_dc<PP, 5>(ctx, items, added_bits, shift, bit_reversed, points, values_out);
-    else fail(P3R_EUNSUPPORTED, "UnsupportedChallengeDegree: the quintic challenge field is KoalaBear's");
-    return;
-  }
-  open_points_dc<PP, 4>(ctx, items, added_bits, shift, bit_reversed, points, values_out);
+  with_challenge_degree<PP>(ctx, [&](auto dc) { open_points_dc<PP, decltype(dc)::value>(ctx, items, added_bits, shift, bit_reversed, points, values_out); });
 }
 
 template void open_points<KoalaBearParams>(p3r_ctx*, const std::vector<OpenPointsItem>&, int, uint32_t, bool, const uint32_t*, uint32_t*);

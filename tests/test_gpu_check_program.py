@@ -1,4 +1,4 @@
-"""GPU: the constraint check (p3r_check_program_dmat, k_check_program) word for word against the integer reference
+"""GPU: the constraint check (p3r_check_program_dmat, k_trace_program<CheckProgSink>) word for word against the integer reference
 tests/check_ref.py: the report, every first failing row and every count.  No tolerance.
 
 The AIR: a Fibonacci table (a, b) - next.a = b and next.b = a + b on transitions, a = public 0 and b = 1 in the first row,
@@ -152,6 +152,56 @@ def test_constraints_that_fail_in_every_row(ctxs, field, dc):
         got = check(ctx, field, dc, b, [rng.integers(0, p, size=(h, 1), dtype=np.uint32)], challenges=chal)
         assert got["n_failed_of"].tolist() == [h, 0, h] and got["first_row_of"].tolist() == [0, NONE, 0]
         assert got["n_failures"] == 2 * h and got["first_row"] == 0 and got["first_constraint"] == 0
+
+
+def full_house(field, dc, n_live, all_ext=False):
+    """n_live values alive at one point (half of them extension values, or all): loaded first, then summed; the sum has to
+    be the extension value of the third matrix.  Widths (3, 2 DC, DC)."""
+    import plonky3_recursion_amd as p3r
+    b = p3r.AirBuilder(field)
+    vals = [(b.local_ext(1, k % (dc + 1)) if all_ext or k % 2 else b.next(0, k % 3)) for k in range(n_live)]
+    acc = vals[0]
+    for v in vals[1:]:
+        acc = acc + v
+    b.assert_zero(acc - b.local_ext(2, 0))
+    return b
+
+
+def full_house_traces(field, dc, h, n_live, all_ext, rng):
+    """Two random matrices and the third that satisfies full_house: the sums, taken over the integers here."""
+    p = ref.P(field)
+    m0, m1 = (rng.integers(0, p, size=(h, w), dtype=np.uint32) for w in (3, 2 * dc))
+    nxt = np.roll(m0, -1, axis=0).astype(np.int64)   # the row after the last is row 0
+    total = np.zeros((h, dc), dtype=np.int64)
+    for k in range(n_live):
+        if all_ext or k % 2:
+            total += m1[:, k % (dc + 1):k % (dc + 1) + dc]
+        else:
+            total[:, 0] += nxt[:, k % 3]
+    return [m0, m1, (total % p).astype(np.uint32)]
+
+
+@pytest.mark.parametrize("field,dc", ref.CTXS)
+def test_a_slot_file_of_extension_values_only(ctxs, field, dc):
+    """P3R_AIR_MAX_LIVE extension values alive at once: a slot file of 48 x DC words for each of the 64 lanes.  In the
+    KoalaBear quintic context that is 60 KiB, above the 48 KiB a kernel gets without asking, so the launch has to ask for
+    it; at degree 4 it is exactly 48 KiB and does not cross the line.  Heights 64 and 128: one workgroup and two.  The
+    satisfying trace passes; with one cell broken the wave that holds it votes and its two atomics run."""
+    from plonky3_recursion_amd import _lib
+    ctx, p = ctxs(field, dc), ref.P(field)
+    rng = np.random.default_rng(1750 + dc)
+    n_live = _lib.P3R_AIR_MAX_LIVE
+    prog = full_house(field, dc, n_live, all_ext=True)
+    assert ctx.air_program_info(prog, (3, 2 * dc, dc))["peak_live"] == n_live
+    for h in (64, 128):
+        mats = full_house_traces(field, dc, h, n_live, True, rng)
+        got = check(ctx, field, dc, prog, mats)
+        assert got["n_failures"] == 0 and got["first_row"] == NONE
+        row = h - 3
+        mats[1][row, 2 * dc - 1] = (int(mats[1][row, 2 * dc - 1]) + 1) % p   # the top word of the last window only
+        got = check(ctx, field, dc, prog, mats)
+        assert got["n_failures"] == 1 and got["first_row"] == row and got["first_constraint"] == 0
+        assert got["n_failed_of"].tolist() == [1] and got["first_row_of"].tolist() == [row]
 
 
 @pytest.mark.parametrize("field,dc", ref.CTXS)

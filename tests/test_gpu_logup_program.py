@@ -1,4 +1,4 @@
-"""GPU: the lookup-program seam (p3r_logup_program_dmat, k_logup_program + k_ef_scan) word for word against the integer
+"""GPU: the lookup-program seam (p3r_logup_program_dmat, k_trace_program<LogupProgSink> + k_ef_scan) word for word against the integer
 reference tests/logup_ref.py.  Every comparison is exact equality of canonical words: the output's width, every word of
 the running sum and of every fraction column, and the table's sum.  No tolerance, no case skipped.
 

@@ -1,4 +1,4 @@
-"""GPU: the lookup check (p3r_lookup_check_dmat: k_lookup_records, the stable radix sort and the exclusive sums of
+"""GPU: the lookup check (p3r_lookup_check_dmat: k_trace_program<RecordSink>, the stable radix sort and the exclusive sums of
 device_prims.hip.h) against the integer reference tests/check_ref.py: the number of unbalanced keys and, entry by entry,
 instance, row and term of the key's first record, the number of its records, the key and the net multiplicity.  No
 tolerance.
@@ -92,6 +92,46 @@ def test_a_balanced_bus_and_one_dropped_send(ctxs, field, dc):
     n, got = check(ctx, field, dc, [spoiled, receiver])   # the other order of the instances: the first record is a send, or the receive
     first_send = [r for r in range(48) if sent[r] == sent[drop] and r != drop]
     assert n == 1 and (got[0]["instance"], got[0]["row"]) == ((0, first_send[0]) if first_send else (1, sent[drop]))
+
+
+def full_house_bus(field, dc, n_live):
+    """A bus over the tuple (column 0, column 1) with the multiplicity in column 2, whose denominator also takes in the
+    sum of n_live extension values - windows of the 2 DC columns from column 3 on - that are all alive at one point."""
+    import plonky3_recursion_amd as p3r
+    b = p3r.AirBuilder(field)
+    vals = [b.local_ext(0, 3 + k % (dc + 1)) for k in range(n_live)]
+    acc = vals[0]
+    for v in vals[1:]:
+        acc = acc + v
+    b.lookup(b.local(0, 2), acc + b.challenge(0) + b.local(0, 0) + b.challenge(1) * b.local(0, 1))
+    b.end_lookup_column()
+    return b
+
+
+@pytest.mark.parametrize("field,dc", ref.CTXS)
+def test_a_slot_file_of_extension_values_only(ctxs, field, dc):
+    """P3R_AIR_MAX_LIVE extension values alive at once: a slot file of 48 x DC words for each of the 64 lanes.  In the
+    KoalaBear quintic context that is 60 KiB, above the 48 KiB a kernel gets without asking, so the launch of
+    k_trace_program<RecordSink> has to ask for it; at degree 4 it is exactly 48 KiB and does not cross the line.  A sender of 128 rows
+    and a receiver of 64: two workgroups and one.  The 2 DC further columns of a row are a function of its tuple, so the
+    key still is one - but a wrong word in any slot of any row unbalances the bus."""
+    from plonky3_recursion_amd import _lib
+    ctx, p = ctxs(field, dc), ref.P(field)
+    rng = np.random.default_rng(1870 + dc)
+    sender, receiver, sent = two_tables(field, rng, hs=128, hr=64)
+    of_tuple = rng.integers(0, p, size=(64, 2 * dc), dtype=np.uint32)
+    rest = rng.integers(0, p, size=(128, 2 * dc), dtype=np.uint32)   # the padding rows keep these: they are no records
+    rest[:len(sent)] = of_tuple[sent]
+    sender, receiver = np.concatenate([sender, rest], axis=1), np.concatenate([receiver, of_tuple], axis=1)
+    prog = full_house_bus(field, dc, _lib.P3R_AIR_MAX_LIVE)
+    assert ctx.lookup_program_info(prog, (3 + 2 * dc,))["peak_live"] == _lib.P3R_AIR_MAX_LIVE
+    n, _ = check(ctx, field, dc, [receiver, sender], progs=[prog, prog])
+    assert n == 0
+    drop = 70
+    sender[drop, 2] = 0
+    n, got = check(ctx, field, dc, [receiver, sender], progs=[prog, prog])
+    assert n == 1 and (got[0]["instance"], got[0]["row"], got[0]["term"]) == (0, sent[drop], 0)
+    assert got[0]["net"] == [p - 1] + [0] * (dc - 1) and got[0]["n_records"] == np.count_nonzero(sent == sent[drop])
 
 
 def direct(field, dc):

@@ -1,4 +1,4 @@
-"""GPU: the multiplicity join (p3r_lookup_multiplicities_dmat: k_lookup_records, the compaction, the stable radix sort,
+"""GPU: the multiplicity join (p3r_lookup_multiplicities_dmat: k_trace_program<RecordSink>, the compaction, the stable radix sort,
 the head marks and the exclusive sums the lookup check runs on, then k_lookup_scatter) against the integer reference
 tests/multiplicity_ref.py: the column cell for cell, the number of misses and the miss list entry for entry.  No
 tolerance.

@@ -215,10 +215,10 @@ def test_a_random_dag_of_200_constraints(ctxs, field, dc):
           challenges=rand_ext(rng, p, dc, 3), alpha=rand_ext(rng, p, dc))
 
 
-def full_house(field, dc, n_live):
-    """n_live values alive at one point, half of them extension values: loaded first, then summed and squared."""
+def full_house(field, dc, n_live, all_ext=False):
+    """n_live values alive at one point (half of them extension values, or all): loaded first, then summed and squared."""
     b = builder(field)
-    vals = [(b.local_ext(1, k % (dc + 1)) if k % 2 else b.next(0, k % 3)) for k in range(n_live)]
+    vals = [(b.local_ext(1, k % (dc + 1)) if all_ext or k % 2 else b.next(0, k % 3)) for k in range(n_live)]
     acc = vals[0]
     for v in vals[1:]:
         acc = acc + v
@@ -245,6 +245,22 @@ def test_exactly_the_live_limit_and_one_more(ctxs, field, dc):
     for d in dm:
         d.free()
     check(ctx, field, dc, prog, mats, added_bits, q, alpha=alpha)
+
+
+@pytest.mark.parametrize("field,dc", ref.CTXS)
+def test_a_slot_file_of_extension_values_only(ctxs, field, dc):
+    """P3R_AIR_MAX_LIVE extension values alive at once: a slot file of 48 x DC words for each of the 64 lanes.  In the
+    KoalaBear quintic context that is 60 KiB, above the 48 KiB a kernel gets without asking, so the launch has to ask for
+    it; at degree 4 it is exactly 48 KiB and does not cross the line.  A trace of 64 rows with blow-up 2 and quotient
+    degree 2: a domain of 128 rows, two workgroups of one wave."""
+    from plonky3_recursion_amd import _lib
+    ctx, p = ctxs(field, dc), ref.P(field)
+    rng = np.random.default_rng(1460 + dc)
+    widths, q, added_bits, h = (3, 2 * dc), 1, 1, 64
+    mats = [rng.integers(0, p, size=(h << added_bits, w), dtype=np.uint32) for w in widths]
+    prog = full_house(field, dc, _lib.P3R_AIR_MAX_LIVE, all_ext=True)
+    assert ctx.air_program_info(prog, widths)["peak_live"] == _lib.P3R_AIR_MAX_LIVE
+    check(ctx, field, dc, prog, mats, added_bits, q, alpha=rand_ext(rng, p, dc))
 
 
 @pytest.mark.parametrize("field,dc", ref.CTXS)

@@ -1,4 +1,4 @@
-"""GPU: the witness seam (p3r_witness_program_dmat: k_witness_program, the interpreter with its fifth sink) word for word
+"""GPU: the witness seam (p3r_witness_program_dmat: k_trace_program<WitnessSink>, the interpreter with its fifth sink) word for word
 against the integer interpreter tests/witness_ref.py.  No tolerance.
 
 The traces: matrix 0 has three base columns - two that walk 0, 1, p - 1, 2^30 from different starts and then random

@@ -14,7 +14,7 @@ are 3 DC words per 1024 rows.  No hardware counter is collected.
 
 For the extension sum the one existing kernel that does the same job stands beside it: k_ef_scan, as
 p3r_logup_program_dmat runs it on a column of the same height.  The existing profile hooks give that entry ONE scope,
-`logup_program`, which holds k_logup_program (one fraction m / d per row: an extension inversion, DC words written twice)
+`logup_program`, which holds k_trace_program<LogupProgSink> (one fraction m / d per row: an extension inversion, DC words written twice)
 and the three scan passes; the passes alone cannot be read through them.  So the figure beside the sum is an upper bound
 of the scan passes.  The two are called ALTERNATELY, in five runs of --reps calls each; the spread of the five medians is
 the run-to-run noise.  Nothing here is a threshold; the output goes to profiles/<round>/."""
@@ -111,7 +111,7 @@ def main():
         runs["logup_program"].append(statistics.median(l))
     lines.append("-- ext sum beside p3r_logup_program_dmat on a column of the same height, alternated; the medians of five runs of %d calls" % a.reps)
     for name, what in (("ext sum", "the three passes of k_affine_scan, pure-sum instance"),
-                       ("logup_program", "k_logup_program (one fraction per row) + the three passes of k_ef_scan: an UPPER bound of the scan passes")):
+                       ("logup_program", "k_trace_program<LogupProgSink> (one fraction per row) + the three passes of k_ef_scan: an UPPER bound of the scan passes")):
         m = runs[name]
         lines.append("%-15s %s; spread %.4f (%.1f%% of the median)   %s"
                      % (name, " ".join("%.4f" % v for v in m), max(m) - min(m), 100.0 * (max(m) - min(m)) / statistics.median(m), what))

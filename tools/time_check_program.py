@@ -1,7 +1,7 @@
 """Times of the two trace checks on resident KoalaBear traces, DC = 4.
    python tools/time_check_program.py [--log-rows 20] [--reps 20] [--out FILE]
 
-1. p3r_check_program_dmat (k_check_program) on a 2^log-rows x 32 trace that does NOT satisfy the program in most rows
+1. p3r_check_program_dmat (k_trace_program<CheckProgSink>) on a 2^log-rows x 32 trace that does NOT satisfy the program in most rows
    (random cells) and on one that satisfies it everywhere (random inputs, the constrained cells computed from them), for
    two programs:
      thin     two constraints over five cells;
@@ -133,7 +133,7 @@ def main():
             assert (rep["n_failures"] == 0) == (mat is good_trace)
             call = median_ms(lambda: ctx.check_device(prog, [mat]), a.reps)
             k = scopes_ms(ctx, lambda: ctx.check_device(prog, [mat]), a.reps, ["check_program"])["check_program"]
-            lines.append("check, %s: %d failures; call %.3f [%.3f .. %.3f], k_check_program %.3f" % ((label, rep["n_failures"]) + call + (k,)))
+            lines.append("check, %s: %d failures; call %.3f [%.3f .. %.3f], k_trace_program<CheckProgSink> %.3f" % ((label, rep["n_failures"]) + call + (k,)))
 
         def quotient():   # the same matrix as the satisfying check's (the pass does not care what its cells mean)
             for c in ctx.quotient_device(prog, [good_trace], added_bits, q, alpha):

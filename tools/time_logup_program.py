@@ -1,4 +1,4 @@
-"""Time of the lookup-program seam (p3r_logup_program_dmat: k_logup_program and the three k_ef_scan passes) on a resident
+"""Time of the lookup-program seam (p3r_logup_program_dmat: k_trace_program<LogupProgSink> and the three k_ef_scan passes) on a resident
 KoalaBear trace of 2^20 rows, DC = 4: 8 terms in 4 columns, each term a multiplicity cell over the reference's bus
 denominator bus_prefix + t0 + beta * t1 of two cells - 24 input columns.
    python tools/time_logup_program.py [--log-rows 20] [--reps 10] [--bench-detail FILE] [--out FILE]
@@ -85,7 +85,7 @@ def main():
     mont = float(re.search(r"Montgomery product\s+([0-9.]+) T", rates).group(1)) * 1e12
     lines = ["lookup program over a 2^%d-row KoalaBear trace, DC = %d: %d terms in %d columns, %d input columns, %d instructions, %d live values at most"
              % (a.log_rows, dc, TERMS, COLUMNS, width, len(prog.insns), info["peak_live"]),
-             "call %.3f ms (upload of the program, four launches, the wait for the table's sum); launches %.3f ms (scope logup_program: k_logup_program + 3 x k_ef_scan)"
+             "call %.3f ms (upload of the program, four launches, the wait for the table's sum); launches %.3f ms (scope logup_program: k_trace_program<LogupProgSink> + 3 x k_ef_scan)"
              % (call_ms, k_ms),
              "must move %.1f MB read + %.1f MB written = %.1f MB: %.1f GB/s over the launches, %.3f of HBM %d GB/s"
              % (read / 1e6, written / 1e6, (read + written) / 1e6, (read + written) / k_ms / 1e6, (read + written) / k_ms / 1e6 / HBM_GBS, HBM_GBS),
